@@ -7,9 +7,14 @@ Workload (config.workload): BASELINE configs[1] shape (human-segmentation net: C
 C_width=128, K=128, N_block=4, per-face outputs, dropout on) at the north-star size
 (>=10k-vertex meshes, batch of meshes).
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (milliseconds per timed step), the
+configuration.  A plain run sets up, warms up, times --steps steps and prints that line, nothing else.  With --full the line also holds
   roofline     -- dominant kernel family, algorithmic flops (or bytes) / hipEvent-measured duration
+  parity       -- the product path against the reference's own outputs (committed fixtures), measured in this run
   cpu_baseline -- the CPU oracle (torch-CPU restatement of the reference) on a bounded sample
+and the diffusion-block bandwidth, the all-reduce alone (N > 1) and short runs of the other BASELINE configs.
+--dump-outputs DIR writes what the last timed step computed (loss, log-probabilities, updated parameters, gradients) as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -53,6 +58,33 @@ def build_batch(sizes, K, device, seed0):
     gather = GatherPattern(faces, sum(sizes))
     x = torch.cat([m["verts"] for m in meshes], 0).to(device)
     return meshes, mb, gather, x
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (float64 kept), at most DUMP_BUDGET_BYTES in all.  The smaller arrays
+    are written whole; an array beyond what is left of the budget is written as a fixed sample of its rows (seeded, sorted) with the row
+    indices next to it as <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 4096 * 2 * len(arrays)          # (headroom for the .npy headers)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.dim() > 0 and t.numel() * t.element_size() > share:
+            row_bytes = (t.numel() // max(1, t.shape[0])) * t.element_size() + 8
+            n_keep = max(1, min(t.shape[0], share // row_bytes))
+            g = torch.Generator().manual_seed(0)
+            rows = torch.randperm(t.shape[0], generator=g)[:n_keep].sort().values
+            t = t[rows.to(t.device)]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.double().numpy())
+            left -= n_keep * 8
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+        left -= t.numel() * t.element_size()
 
 
 def _import_reference():
@@ -546,8 +578,13 @@ def main():
     ap.add_argument("--keig", type=int, default=128)
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--streams", type=int, default=1, help="split the per-GPU batch into this many sub-batches run on separate HIP streams")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="headline at 1 GPU: do not append the short runs of cfg2..cfg5 (`configs` object)")
+    ap.add_argument("--full", action="store_true", help="headline: after the timed steps also measure and report the roofline / kernel families, "
+                                                        "the diffusion block, in-run parity, the all-reduce alone (N > 1), the CPU and "
+                                                        "PyTorch-ROCm baselines and the other configs (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="headline / cfg5: write what the last timed step computed (loss, "
+                                                                         "log-probabilities, updated parameters, gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU and PyTorch-ROCm baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, headline at 1 GPU: do not append the short runs of cfg2..cfg5 (`configs` object)")
     ap.add_argument("--graph", action="store_true", help="cfg2/cfg3: replay a captured HIP graph of the step (diffusion_net.graphs) instead of enqueueing ~150 launches per step "
                                                          "(the headline step is replayed from a graph by default; see --eager)")
     ap.add_argument("--graph-collectives", action="store_true", help="N > 1: capture the bucketed RCCL all-reduce inside the step graph instead of issuing one flat all-reduce from the host after the replay")
@@ -560,6 +597,8 @@ def main():
                     help="headline: BASELINE metric workload (default, what the driver runs); cfg2/cfg3/cfg4: the other BASELINE.json configs, same JSON contract; "
                          "cfg5: the headline step at the rna_mesh_segmentation shape (8 meshes x ~15k vertices per GPU, 260 classes at the vertices; works with --gpus N)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.config not in ("headline", "cfg5") or args.epoch > 0):
+        ap.error("--dump-outputs is implemented for the headline step (and cfg5), not for --config %s / --epoch" % args.config)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU of this node over RCCL, same arguments
@@ -700,23 +739,29 @@ def main():
                 blk._graph_seed = None
             gs, step_mode = None, "eager launches (graph capture failed: %s)" % why
 
+    last_preds = []                            # eager steps: the log-probabilities of the last step (a graph keeps its own: gs.preds)
+
     def step():
         if gs is not None:
             return gs.step()
         flat.zero_grad()
         if nsub == 1:
             mb_j, gather_j, x_j, labels_j, _ = subs[0]
-            _, loss = model.forward_packed_loss(x_j, mb_j, gather_j, labels_j)     # per-face log-softmax + NLL: one kernel each way
+            preds, loss = model.forward_packed_loss(x_j, mb_j, gather_j, labels_j)     # per-face log-softmax + NLL: one kernel each way
+            last_preds[:] = [preds]
             loss.backward()
         else:
             # sub-batches on separate streams: the store phase of one overlaps the MFMA phase of the other;
             # gradients of all sub-batches accumulate into the same flat bucket (mean over the whole batch)
             cur = torch.cuda.current_stream(device)
             losses = []
+            last_preds.clear()
             for st, (mb_j, gather_j, x_j, labels_j, v_j) in zip(streams, subs):
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
-                    losses.append(model.forward_packed_loss(x_j, mb_j, gather_j, labels_j)[1] * (1.0 / nsub))
+                    preds_j, loss_j = model.forward_packed_loss(x_j, mb_j, gather_j, labels_j)
+                    last_preds.append(preds_j)
+                    losses.append(loss_j * (1.0 / nsub))
             for st, l in zip(streams, losses):
                 with torch.cuda.stream(st):
                     l.backward()
@@ -736,24 +781,28 @@ def main():
         step()
     fence()
     lib.dn_prof_reset()
-    lib.dn_prof_enable(1)
+    lib.dn_prof_enable(1 if args.full else 0)  # --full: the library's event brackets (eager launches only) feed kernel_families
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     fence()
     elapsed = time.perf_counter() - t0
     lib.dn_prof_enable(0)
-    multi = None
+    if args.dump_outputs and rank == 0:        # before anything else runs on the model: the last timed step's results as a caller gets them
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "log_probs": gs.preds if gs is not None else torch.cat(last_preds, 0),
+                                         "params": flat.master, "grads": flat.grad})
+    multi, v_all = None, float(v_step)
     if world > 1:
         mine = torch.tensor([elapsed], device=device, dtype=torch.float64)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)                       # every rank's own clock over the same K steps: a straggler shows here, not only in the MAX
         t = mine.clone()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         vt = torch.tensor([v_step], device=device, dtype=torch.float64)
         dist.all_reduce(vt, op=dist.ReduceOp.SUM)
         v_all = float(vt.item())
+    if world > 1 and args.full:
+        every = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(every, mine)                       # every rank's own clock over the same K steps: a straggler shows here, not only in the MAX
         # the gradient all-reduce by itself (outside the timed region): the flat bucket as the step sends it, K times between two fences --
         # so that the first real N-GPU run says how much of its step is the collective and how much is the ranks waiting for each other
         fence()
@@ -769,109 +818,109 @@ def main():
                                        else ("captured with the step, per-block buckets overlapped with the backward" if gs is not None else
                                              "per-block buckets launched from inside backward (eager)"),
                  "backend": dist.get_backend()}
-    else:
-        v_all = float(v_step)
     assert torch.isfinite(loss).item()
 
-    eager_ms = None
-    if gs is not None:      # the library's per-launch event brackets are host-side: time the same launches in a short eager pass
-        lib.dn_prof_reset()
-        lib.dn_prof_enable(1)
-        te = time.perf_counter()
-        for _ in range(min(args.steps, 5)):
-            gs._body()
-            gs._tail()
-        fence()
-        eager_ms = 1e3 * (time.perf_counter() - te) / min(args.steps, 5)
-        lib.dn_prof_enable(0)
-    fam, roof = kernel_family_report(lib)
-    if roof is not None:
-        fam_ms = sum(f["ms_total"] for f in fam) / (min(args.steps, 5) if gs is not None else args.steps)
-        roof["timing"] = ("HIP events around every launch of %d eager steps run right after the timed graph replays (the event brackets are "
-                          "host-side; a replayed graph bypasses them); profiles/ holds the rocprofv3 kernel trace of the replays themselves"
-                          % min(args.steps, 5)) if gs is not None else "HIP events around every launch of the timed steps"
-        # the brackets inflate: event records sit between the launches and the eager pass has host gaps the replay does not
-        roof["families_ms_per_step"] = fam_ms
-        roof["bracket_inflation_vs_timed_step"] = fam_ms / (1e3 * elapsed / args.steps)
-        # real inter-kernel idle of the TIMED (replayed) step = step time - sum of kernel time.  The sum here is the library's own kernels from the
-        # bracketed eager pass (torch's fill / Adam kernels, ~0.1 ms, are not bracketed; a bracket also counts the launch ramp), so the
-        # difference is an upper bound of the idle only when positive; rocprofv3's per-kernel durations of the replays are the reference
-        # (profiles/r0N_step_kernels.txt: the profiler itself inserts ~10 us between kernels, which the unprofiled replay does not have)
-        roof["timed_step_ms_minus_bracketed_kernel_ms"] = 1e3 * elapsed / args.steps - fam_ms
-        if eager_ms is not None:
-            roof["eager_pass_ms_per_step"] = eager_ms
-
-    # ---- diffusion block (to_basis + exp(-lambda t) + from_basis) on the same batch: HBM GB/s of BASELINE.json
-    from diffusion_net import ops
     Cw, K = args.cwidth, args.keig
-    v_sub0 = subs[0][4]
-    sizes = sizes[0::nsub]
-    tt = torch.full((Cw,), 0.05, device=device)
-    bytes_diff = sum(4.0 * (v * (2 * Cw + 2 * K + 1) + 2 * K * Cw + K + Cw) for v in sizes)
-    flops_diff = sum(4.0 * v * K * Cw for v in sizes)
+    fam, roof, diff = [], None, None
+    if args.full:
+        eager_ms = None
+        if gs is not None:      # the library's per-launch event brackets are host-side: time the same launches in a short eager pass
+            lib.dn_prof_reset()
+            lib.dn_prof_enable(1)
+            te = time.perf_counter()
+            for _ in range(min(args.steps, 5)):
+                gs._body()
+                gs._tail()
+            fence()
+            eager_ms = 1e3 * (time.perf_counter() - te) / min(args.steps, 5)
+            lib.dn_prof_enable(0)
+        fam, roof = kernel_family_report(lib)
+        if roof is not None:
+            fam_ms = sum(f["ms_total"] for f in fam) / (min(args.steps, 5) if gs is not None else args.steps)
+            roof["timing"] = ("HIP events around every launch of %d eager steps run right after the timed graph replays (the event brackets are "
+                              "host-side; a replayed graph bypasses them); profiles/ holds the rocprofv3 kernel trace of the replays themselves"
+                              % min(args.steps, 5)) if gs is not None else "HIP events around every launch of the timed steps"
+            # the brackets inflate: event records sit between the launches and the eager pass has host gaps the replay does not
+            roof["families_ms_per_step"] = fam_ms
+            roof["bracket_inflation_vs_timed_step"] = fam_ms / (1e3 * elapsed / args.steps)
+            # real inter-kernel idle of the TIMED (replayed) step = step time - sum of kernel time.  The sum here is the library's own kernels from the
+            # bracketed eager pass (torch's fill / Adam kernels, ~0.1 ms, are not bracketed; a bracket also counts the launch ramp), so the
+            # difference is an upper bound of the idle only when positive; rocprofv3's per-kernel durations of the replays are the reference
+            # (profiles/r0N_step_kernels.txt: the profiler itself inserts ~10 us between kernels, which the unprofiled replay does not have)
+            roof["timed_step_ms_minus_bracketed_kernel_ms"] = 1e3 * elapsed / args.steps - fam_ms
+            if eager_ms is not None:
+                roof["eager_pass_ms_per_step"] = eager_ms
 
-    def time_diffusion(n_rot):
-        # n_rot input buffers touched in turn (the eigenbasis itself is one 81 MB array: it is re-read from HBM only when the inputs and
-        # outputs streaming past it evict it from the 256 MiB Infinity Cache, as in the network)
-        xs_ = [torch.randn(v_sub0, Cw, device=device) for _ in range(n_rot)]
-        with torch.no_grad():
+        # ---- diffusion block (to_basis + exp(-lambda t) + from_basis) on the same batch: HBM GB/s of BASELINE.json
+        from diffusion_net import ops
+        v_sub0 = subs[0][4]
+        sizes = sizes[0::nsub]
+        tt = torch.full((Cw,), 0.05, device=device)
+        bytes_diff = sum(4.0 * (v * (2 * Cw + 2 * K + 1) + 2 * K * Cw + K + Cw) for v in sizes)
+        flops_diff = sum(4.0 * v * K * Cw for v in sizes)
+
+        def time_diffusion(n_rot):
+            # n_rot input buffers touched in turn (the eigenbasis itself is one 81 MB array: it is re-read from HBM only when the inputs and
+            # outputs streaming past it evict it from the 256 MiB Infinity Cache, as in the network)
+            xs_ = [torch.randn(v_sub0, Cw, device=device) for _ in range(n_rot)]
+            with torch.no_grad():
+                for i in range(3):
+                    ops.DiffusionFn.apply(xs_[i % n_rot], tt, mb)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                reps = 24
+                keep = []
+                for i in range(reps):
+                    keep.append(ops.DiffusionFn.apply(xs_[i % n_rot], tt, mb))
+                    if len(keep) > n_rot:
+                        keep.pop(0)
+                e1.record()
+                torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e-3 / reps
+        t_diff = time_diffusion(8)        # 8 inputs + 8 live outputs x 81 MB = 1.3 GB in rotation: HBM
+        t_diff_cached = time_diffusion(1)
+
+        def time_diffusion_bwd(n_rot):
+            # the gradient of the same operator (dn_diffusion_bwd_f32: d_x = add + M Phi (coef * Phi^T d_xd), d_time), called as ops.DiffusionFn.backward calls it
+            Lb = _hip.lib()
+            gs_ = [torch.randn(v_sub0, Cw, device=device) for _ in range(n_rot)]
+            adds = [torch.randn(v_sub0, Cw, device=device) for _ in range(n_rot)]
+            outs = [torch.empty(v_sub0, Cw, device=device) for _ in range(n_rot)]
+            xs_sp = torch.randn(mb.n_mesh, K, Cw, device=device)
+            d_t = torch.empty(Cw, device=device)
+            nws = Lb.dn_diffusion_workspace_bytes(mb.ref(), Cw)
+            ws_ = torch.empty(nws + 4096, dtype=torch.uint8, device=device)
+            st_ = torch.cuda.current_stream(device).cuda_stream
+
+            def call(i):
+                _hip.check(Lb.dn_diffusion_bwd_f32(mb.ref(), gs_[i % n_rot].data_ptr(), xs_sp.data_ptr(), tt.data_ptr(), Cw, adds[i % n_rot].data_ptr(),
+                                                   outs[i % n_rot].data_ptr(), d_t.data_ptr(), ws_.data_ptr(), nws, st_), "dn_diffusion_bwd_f32")
             for i in range(3):
-                ops.DiffusionFn.apply(xs_[i % n_rot], tt, mb)
+                call(i)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            reps = 24
-            keep = []
-            for i in range(reps):
-                keep.append(ops.DiffusionFn.apply(xs_[i % n_rot], tt, mb))
-                if len(keep) > n_rot:
-                    keep.pop(0)
+            for i in range(24):
+                call(i)
             e1.record()
             torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e-3 / reps
-    t_diff = time_diffusion(8)        # 8 inputs + 8 live outputs x 81 MB = 1.3 GB in rotation: HBM
-    t_diff_cached = time_diffusion(1)
-
-    def time_diffusion_bwd(n_rot):
-        # the gradient of the same operator (dn_diffusion_bwd_f32: d_x = add + M Phi (coef * Phi^T d_xd), d_time), called as ops.DiffusionFn.backward calls it
-        Lb = _hip.lib()
-        gs_ = [torch.randn(v_sub0, Cw, device=device) for _ in range(n_rot)]
-        adds = [torch.randn(v_sub0, Cw, device=device) for _ in range(n_rot)]
-        outs = [torch.empty(v_sub0, Cw, device=device) for _ in range(n_rot)]
-        xs_sp = torch.randn(mb.n_mesh, K, Cw, device=device)
-        d_t = torch.empty(Cw, device=device)
-        nws = Lb.dn_diffusion_workspace_bytes(mb.ref(), Cw)
-        ws_ = torch.empty(nws + 4096, dtype=torch.uint8, device=device)
-        st_ = torch.cuda.current_stream(device).cuda_stream
-
-        def call(i):
-            _hip.check(Lb.dn_diffusion_bwd_f32(mb.ref(), gs_[i % n_rot].data_ptr(), xs_sp.data_ptr(), tt.data_ptr(), Cw, adds[i % n_rot].data_ptr(),
-                                               outs[i % n_rot].data_ptr(), d_t.data_ptr(), ws_.data_ptr(), nws, st_), "dn_diffusion_bwd_f32")
-        for i in range(3):
-            call(i)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(24):
-            call(i)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e-3 / 24
-    t_dbwd = time_diffusion_bwd(6)     # 6 x (d_xd, addend, d_x) x 81 MB = 1.5 GB in rotation
-    bytes_dbwd = sum(4.0 * (v * (3 * Cw + 2 * K + 1) + 3 * K * Cw + K + Cw) for v in sizes)   # read d_xd, Phi twice, the addend, mass; write d_x; 3 x (K, C)
-    diff = {"ms": t_diff * 1e3, "gbps": bytes_diff / t_diff / 1e9, "frac_hbm_8TBs": bytes_diff / t_diff / 1e9 / PEAK_HBM_GBPS,
-            "frac_of_measured_copy_6p3TBs": bytes_diff / t_diff / 1e9 / 6300.0,
-            "buffers": "8 rotating input / output sets (1.3 GB): operands come from HBM as inside the network; one re-used set (Infinity-Cache assisted): "
-                       "%.3f ms = %.3f of 8 TB/s" % (t_diff_cached * 1e3, bytes_diff / t_diff_cached / 1e9 / PEAK_HBM_GBPS),
-            "copy_calibration": "hand-written float4 nontemporal copy on 2 GiB of rotating buffers: 6.2-6.36 TB/s = 0.79 of 8 TB/s; hipMemcpy D2D 5.3 TB/s "
-                                "(tools/kbench --ops copyk, profiles/r03_copy_calibration.txt)",
-            "backward": {"ms": t_dbwd * 1e3, "gbps": bytes_dbwd / t_dbwd / 1e9, "frac_hbm_8TBs": bytes_dbwd / t_dbwd / 1e9 / PEAK_HBM_GBPS,
-                         "what": "dn_diffusion_bwd_f32 with an addend (the block's residual gradient), 6 rotating operand sets; algorithmic bytes "
-                                 "4 [V (3C + 2K + 1) + 3KC + K + C] per mesh"},
-            "launches": "projection (split-V, k-major bf16 planes) + per-mesh partial sum with exp(-lambda t) + direct back-projection (dn_diffuse.hip: backproject_kernel)"
-                        if _hip.get_option("diffuse") == 2 else ("one persistent launch (dn_diffuse.hip: diffuse_kernel)" if _hip.get_option("diffuse") == 1 else
-                                                                  "projection + per-mesh partial sum + wave-specialised row GEMM"),
-            "tflops": flops_diff / t_diff / 1e12, "frac_mfma_f32": flops_diff / t_diff / 1e12 / PEAK_MFMA_F32_TFLOPS,
-            "frac_mfma_bf16x3": flops_diff / t_diff / 1e12 / (PEAK_MFMA_BF16_TFLOPS / 6.0),
-            "note": "arithmetic intensity KC/(2(K+C)) = %.0f flop/B; ridge 19.7 (f32 MFMA) / 52 (split-bf16 MFMA, used) -> HBM-bound" % (K * Cw / (2.0 * (K + Cw)))}
+            return e0.elapsed_time(e1) * 1e-3 / 24
+        t_dbwd = time_diffusion_bwd(6)     # 6 x (d_xd, addend, d_x) x 81 MB = 1.5 GB in rotation
+        bytes_dbwd = sum(4.0 * (v * (3 * Cw + 2 * K + 1) + 3 * K * Cw + K + Cw) for v in sizes)   # read d_xd, Phi twice, the addend, mass; write d_x; 3 x (K, C)
+        diff = {"ms": t_diff * 1e3, "gbps": bytes_diff / t_diff / 1e9, "frac_hbm_8TBs": bytes_diff / t_diff / 1e9 / PEAK_HBM_GBPS,
+                "frac_of_measured_copy_6p3TBs": bytes_diff / t_diff / 1e9 / 6300.0,
+                "buffers": "8 rotating input / output sets (1.3 GB): operands come from HBM as inside the network; one re-used set (Infinity-Cache assisted): "
+                           "%.3f ms = %.3f of 8 TB/s" % (t_diff_cached * 1e3, bytes_diff / t_diff_cached / 1e9 / PEAK_HBM_GBPS),
+                "copy_calibration": "hand-written float4 nontemporal copy on 2 GiB of rotating buffers: 6.2-6.36 TB/s = 0.79 of 8 TB/s; hipMemcpy D2D 5.3 TB/s "
+                                    "(tools/kbench --ops copyk, profiles/r03_copy_calibration.txt)",
+                "backward": {"ms": t_dbwd * 1e3, "gbps": bytes_dbwd / t_dbwd / 1e9, "frac_hbm_8TBs": bytes_dbwd / t_dbwd / 1e9 / PEAK_HBM_GBPS,
+                             "what": "dn_diffusion_bwd_f32 with an addend (the block's residual gradient), 6 rotating operand sets; algorithmic bytes "
+                                     "4 [V (3C + 2K + 1) + 3KC + K + C] per mesh"},
+                "launches": "projection (split-V, k-major bf16 planes) + per-mesh partial sum with exp(-lambda t) + direct back-projection (dn_diffuse.hip: backproject_kernel)"
+                            if _hip.get_option("diffuse") == 2 else ("one persistent launch (dn_diffuse.hip: diffuse_kernel)" if _hip.get_option("diffuse") == 1 else
+                                                                      "projection + per-mesh partial sum + wave-specialised row GEMM"),
+                "tflops": flops_diff / t_diff / 1e12, "frac_mfma_f32": flops_diff / t_diff / 1e12 / PEAK_MFMA_F32_TFLOPS,
+                "frac_mfma_bf16x3": flops_diff / t_diff / 1e12 / (PEAK_MFMA_BF16_TFLOPS / 6.0),
+                "note": "arithmetic intensity KC/(2(K+C)) = %.0f flop/B; ridge 19.7 (f32 MFMA) / 52 (split-bf16 MFMA, used) -> HBM-bound" % (K * Cw / (2.0 * (K + Cw)))}
 
     if rank == 0:
         res = {
@@ -881,23 +930,24 @@ def main():
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "arithmetic": "fp32 storage, accumulation and epilogues; dense products on split MFMA with fp32-level accuracy: " + _engine_note() +
-                          " (measured in this run against the reference's own outputs: see \"parity\")",
+                          (" (measured in this run against the reference's own outputs: see \"parity\")" if args.full and world == 1 else ""),
             "config": {"workload": "train step (fwd+NLL+bwd+Adam%s) on a ragged batch of %d meshes x ~%d vertices per GPU, "
                                    "DiffusionNet C_in=3 C_out=%d C_width=%d K=%d N_block=%d outputs_at=%s dropout=on"
                                    % ("+RCCL all-reduce" if world > 1 else "", args.meshes, args.verts, C_out, Cw, K, args.blocks, "faces" if at_faces else "vertices"),
                        "baseline_config": args.config, "meshes_per_gpu": args.meshes, "verts_per_gpu_step": v_step, "parallelism": "dp%d" % world,
                        "streams_per_gpu": nsub, "step_mode": step_mode, **({"sharding": shard_note} if shard_note else {}),
                        **({"TEST_ONLY": "all ranks share GPU 0, gloo collectives (DN_BENCH_TEST_SHARED_GPU)"} if shared_gpu else {})},
-            "roofline": roof, "kernel_families": fam, "diffusion_block": diff,
         }
+        if args.full:
+            res.update({"roofline": roof, "kernel_families": fam, "diffusion_block": diff})
         if multi is not None:
             res["multi_gpu"] = multi
-        if world == 1:
+        if args.full and world == 1:
             res["parity"] = parity_in_run(device)
-        if not args.no_cpu_baseline and world == 1 and args.config == "headline":   # reported at N = 1 only (the other ranks would sit idle behind it)
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "headline":   # reported at N = 1 only (the other ranks would sit idle behind it)
             res["cpu_baseline"] = cpu_baseline(args, C_out, mesh_sizes(args.meshes, args.verts, 0))
             res["torch_rocm_baseline"] = torch_rocm_baseline(args, C_out, mesh_sizes(args.meshes, args.verts, 0), device)
-        if world == 1 and args.config == "headline" and not args.no_other_configs:
+        if args.full and world == 1 and args.config == "headline" and not args.no_other_configs:
             del gs, model, flat, subs, mb            # hand the GPU's memory back before the other configs' processes start
             torch.cuda.empty_cache()
             res["configs"] = other_configs_brief(args)

@@ -471,6 +471,33 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(dev):
     assert 1.0 <= sh["load_imbalance_max_over_mean"] < 1.25 and d["value"] > 0
 
 
+def test_bench_plain_run_and_dump_outputs(dev, tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and reports the headline alone (roofline, parity, baselines and the other
+    configs are behind --full); --dump-outputs writes what the last timed step computed, identically for identical arguments."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--meshes", "2",
+                            "--verts", "3000", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        res = lines[0]
+        assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0, res
+        assert res["unit"] == "vertices/s" and res["higher_is_better"] is True and res["dtype"] == "f32", res
+        assert not {"roofline", "kernel_families", "diffusion_block", "parity", "cpu_baseline", "configs", "epoch_mode"} & set(res), sorted(res)
+        outs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert sorted(outs[0]) == ["grads.npy", "log_probs.npy", "loss.npy", "params.npy"], sorted(outs[0])
+    assert outs[0]["log_probs.npy"].shape[1] == 8 and all(np.isfinite(a).all() for a in outs[0].values())
+    for f in outs[0]:
+        assert np.array_equal(outs[0][f], outs[1][f]), f
+
+
 def test_run_to_run_determinism_stress(dev):
     """Every op of the block, repeated on identical inputs at a multi-mesh 128-wide shape, must be bitwise identical every
     time (tools/determinism_stress.py; this is the test that exposes stale-register / packed-op hazards that stay far

@@ -1,11 +1,11 @@
 #!/bin/bash
-# SQ counter passes (counters only + kernel trace, separate rocprofv3 runs) over tools/kbench ops; summaries -> gpurun_out/pmck_*.txt
+# SQ counter passes (counters only + kernel trace, separate rocprofv3 runs) over tools/kbench ops; summaries -> $DN_OUT_DIR/pmck_*.txt (default out/)
 #   OPS=from_basis,linear LIB=path.so [KARGS="--meshes 1 --verts 200000 --C 256 --K 256"] bash tools/pmc_kbench.sh
-R=${GRAFT_REPO_ROOT:-$(pwd)}
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$(mkdir -p "${DN_OUT_DIR:-$R/out}" && cd "${DN_OUT_DIR:-$R/out}" && pwd)
 OPS=${OPS:-from_basis}
 LIB=${LIB:-$R/diffusion-net_amd/diffusion_net/libdiffnet_hip.so}
 TAG=${TAG:-k}
-mkdir -p "$R/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 run_pass() {  # name, counters...
   name=$1; shift
@@ -13,7 +13,7 @@ run_pass() {  # name, counters...
   timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmck_$name -o p -- "$R/tools/kbench" --lib "$LIB" --reps 3 --ops "$OPS" $KARGS > /tmp/pmck_$name.log 2>&1
   f=$(find /tmp/pmck_$name -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then
-    python3 - "$f" > "$R/gpurun_out/pmck_${TAG}_$name.txt" <<'PY'
+    python3 - "$f" > "$OUT/pmck_${TAG}_$name.txt" <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.Counter()
@@ -31,4 +31,4 @@ PY
 run_pass sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
 run_pass sq2 SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE
 run_pass sq3 SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_INSTS_SMEM SQ_WAVES
-cat "$R"/gpurun_out/pmck_${TAG}_sq*.txt | cut -c1-240
+cat "$OUT"/pmck_${TAG}_sq*.txt | cut -c1-240

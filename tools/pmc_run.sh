@@ -1,7 +1,7 @@
 #!/bin/bash
-# PMC pass (counters only, with kernel-trace) over the per-op microbench; summaries -> gpurun_out/pmc_*.txt
-R=${GRAFT_REPO_ROOT:-$(pwd)}
-mkdir -p "$R/gpurun_out"
+# PMC pass (counters only, with kernel-trace) over the per-op microbench; summaries -> $DN_OUT_DIR/pmc_*.txt (default out/)
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$(mkdir -p "${DN_OUT_DIR:-$R/out}" && cd "${DN_OUT_DIR:-$R/out}" && pwd)
 cd /tmp && export TMPDIR=/tmp
 run_pass() {  # name, counters...
   name=$1; shift
@@ -9,7 +9,7 @@ run_pass() {  # name, counters...
   timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmc_$name -o p -- python "$R/tools/microbench.py" --reps 3 > /tmp/pmc_$name.log 2>&1
   f=$(find /tmp/pmc_$name -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then
-    python - "$f" > "$R/gpurun_out/pmc_$name.txt" <<'PY'
+    python - "$f" > "$OUT/pmc_$name.txt" <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.Counter()
@@ -27,9 +27,9 @@ PY
 if [ -n "$ONLY_TRAFFIC" ]; then
 run_pass fetch FETCH_SIZE
 run_pass write WRITE_SIZE
-head -16 "$R/gpurun_out/pmc_fetch.txt" | cut -c1-140; head -16 "$R/gpurun_out/pmc_write.txt" | cut -c1-140
+head -16 "$OUT/pmc_fetch.txt" | cut -c1-140; head -16 "$OUT/pmc_write.txt" | cut -c1-140
 exit 0
 fi
 run_pass sq SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
 run_pass sq2 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE
-head -40 "$R/gpurun_out/pmc_sq.txt"; head -40 "$R/gpurun_out/pmc_sq2.txt"
+head -40 "$OUT/pmc_sq.txt"; head -40 "$OUT/pmc_sq2.txt"
