@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -17,16 +17,16 @@ from .batch import GatherPattern, MeshBatch, register_handle
 
 
 def _on_device(fn):
-    """Run a Function's forward/backward with the tensors' device current: the library reads the current device for its
+    """Run a Function's forward/backward (or a custom operator of torchlib.py) with the tensors' device current: the library reads the current device for its
     per-device function attributes and CU counts, and a launch on another device's stream is an error -- `model.to('cuda:1')`
     without a surrounding `torch.cuda.device` must just work, as it does for torch's own ops."""
     @functools.wraps(fn)
-    def wrapped(ctx, *args):
+    def wrapped(*args):
         dev = next((a.device for a in args if isinstance(a, torch.Tensor) and a.is_cuda), None)
         if dev is None or torch.cuda.current_device() == dev.index:
-            return fn(ctx, *args)
+            return fn(*args)
         with torch.cuda.device(dev):
-            return fn(ctx, *args)
+            return fn(*args)
     return wrapped
 
 
@@ -258,52 +258,58 @@ def _deliver(sinks, grads):
     return [g if s is None else None for s, g in zip(sinks, grads)]
 
 
+def linear_fwd(mb, x, W, b):
+    """-> (out, word | None).  first_lin (thin input -> block width): its kernel leaves max |out| in a device word for block 0's
+    split-fp16 engine for free"""
+    out = torch.empty(x.shape[0], W.shape[0], dtype=torch.float32, device=x.device)
+    word = torch.zeros(1, dtype=torch.float32, device=x.device) if (W.shape[1] <= 16 and W.shape[0] >= 128 and _amax_tags_on()) else None
+    _hip.check(_hip.lib().dn_linear_fwd_amax_f32(mb.ref(), x.data_ptr(), W.shape[1], W.data_ptr(), b.data_ptr(), W.shape[0],
+                                                 0, None, out.data_ptr(), _hip.ptr(word), _hip.stream_of(x)), "dn_linear_fwd_amax_f32")
+    return out, word
+
+
+def linear_bwd(mb, d_out, x, W, dW, db, want_dx=True):
+    """dW, db: the caller's output buffers -> (d_x | None, word | None).  last_lin (block width -> a few classes): the input
+    gradient's magnitude for the last block's backward, likewise for free"""
+    L = _hip.lib()
+    C_out, C_in = W.shape
+    d_x = torch.empty_like(x) if want_dx else None
+    ws, n = _ws(mb, L.dn_linear_workspace_bytes(mb.ref(), C_in, C_out))
+    word = torch.zeros(1, dtype=torch.float32, device=x.device) if (want_dx and C_out <= 16 and C_in >= 128 and _amax_tags_on()) else None
+    _hip.check(L.dn_linear_bwd_amax_f32(mb.ref(), d_out.data_ptr(), x.data_ptr(), W.data_ptr(), C_in, C_out, _hip.ptr(d_x),
+                                        dW.data_ptr(), db.data_ptr(), _hip.ptr(word), ws.data_ptr(), n, _hip.stream_of(d_out)),
+               "dn_linear_bwd_amax_f32")
+    return d_x, word
+
+
 class LinearFn(torch.autograd.Function):
     @staticmethod
     @_on_device
     def forward(ctx, x, W, b, mb):
         _require(x, mb)
         ctx.sinks = _sinks([W, b])
-        x, W, b = _f32c(x), _f32c(W), _f32c(b)
-        out = torch.empty(x.shape[0], W.shape[0], dtype=torch.float32, device=x.device)
-        # first_lin (thin input -> block width): its kernel leaves max |out| in a device word for block 0's split-fp16 engine for free
-        word = torch.zeros(1, dtype=torch.float32, device=x.device) if (W.shape[1] <= 16 and W.shape[0] >= 128 and _amax_tags_on()) else None
-        _hip.check(_hip.lib().dn_linear_fwd_amax_f32(mb.ref(), x.data_ptr(), W.shape[1], W.data_ptr(), b.data_ptr(), W.shape[0],
-                                                     0, None, out.data_ptr(), _hip.ptr(word), _hip.stream_of(x)), "dn_linear_fwd_amax_f32")
+        x, W = _f32c(x), _f32c(W)
+        out, word = linear_fwd(mb, x, W, _f32c(b))
         ctx.mb = mb
         ctx.save_for_backward(x, W)
-        if word is not None:
-            _tag_amax(out, word)
-        return out
+        return _tag_amax(out, word)
 
     @staticmethod
     @_on_device
     def backward(ctx, d_out):
-        L = _hip.lib()
-        mb = ctx.mb
         x, W = ctx.saved_tensors
-        d_out = _f32c(d_out)
-        C_out, C_in = W.shape
-        d_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dW = _grad_out(ctx.sinks[0], W)
-        db = _grad_out(ctx.sinks[1], W.new_empty(C_out))
-        ws, n = _ws(mb, L.dn_linear_workspace_bytes(mb.ref(), C_in, C_out))
-        # last_lin (block width -> a few classes): the input gradient's magnitude for the last block's backward, likewise for free
-        word = torch.zeros(1, dtype=torch.float32, device=x.device) if (d_x is not None and C_out <= 16 and C_in >= 128 and _amax_tags_on()) else None
-        _hip.check(L.dn_linear_bwd_amax_f32(mb.ref(), d_out.data_ptr(), x.data_ptr(), W.data_ptr(), C_in, C_out, _hip.ptr(d_x),
-                                            dW.data_ptr(), db.data_ptr(), _hip.ptr(word), ws.data_ptr(), n, _hip.stream_of(d_out)),
-                   "dn_linear_bwd_amax_f32")
+        db = _grad_out(ctx.sinks[1], W.new_empty(W.shape[0]))
+        d_x, word = linear_bwd(ctx.mb, _f32c(d_out), x, W, dW, db, ctx.needs_input_grad[0])
         dW, db = _deliver(ctx.sinks, [dW, db])
-        if word is not None:
-            _tag_amax(d_x, word)
-        return d_x, dW, db, None
+        return _tag_amax(d_x, word), dW, db, None
 
 
 # ----------------------------------------------------------------------------------------------
 # fused DiffusionNetBlock (layers.py:200-241)
 # ----------------------------------------------------------------------------------------------
 class BlockConfig:
-    """Static description of one block: channel width, MiniMLP sizes, feature switches."""
+    """Static description of one block: channel width, MiniMLP sizes, feature switches.  No call writes to it."""
 
     def __init__(self, C, widths, with_grad, with_rot):
         self.C, self.widths, self.with_grad, self.with_rot = int(C), [int(w) for w in widths], bool(with_grad), bool(with_rot)
@@ -321,7 +327,7 @@ def _params_struct(cfg: BlockConfig, time, A_re, A_im, Ws, bs, masks, x_amax=Non
     p = _hip.BlockParamsStruct()
     p.x_amax, p.out_amax = _hip.ptr(x_amax), _hip.ptr(out_amax)
     p.C, p.n_mlp, p.with_grad, p.with_rot = cfg.C, cfg.n_mlp, int(cfg.with_grad), int(cfg.with_rot)
-    p.flags = int(getattr(cfg, "flags", 0))
+    p.flags = int(cfg.flags)
     for i, w in enumerate(cfg.widths):
         p.widths[i] = w
     p.time, p.A_re, p.A_im = time.data_ptr(), _hip.ptr(A_re), _hip.ptr(A_im)
@@ -360,11 +366,13 @@ def keep_mask_reference(seed: int, layer: int, n_rows: int, width: int):
 def _tag_amax(t, word):
     """Attach the device word holding max |t| to the tensor object (a plain attribute: it lives and dies with that object, so it can
     never describe other data).  Autograd hands the same object on when a gradient has a single consumer; otherwise the tag is simply
-    absent and the consumer measures the tensor itself."""
-    try:
-        t._dn_amax = (word, t.data_ptr(), t._version)
-    except Exception:      # noqa: BLE001
-        pass
+    absent and the consumer measures the tensor itself.  -> t; no word (the call did not track magnitudes): no tag."""
+    if word is not None:
+        try:
+            t._dn_amax = (word, t.data_ptr(), t._version)
+        except Exception:      # noqa: BLE001
+            pass
+    return t
 
 
 def _amax_tags_on():
@@ -386,132 +394,155 @@ def _amax_of(t):
 debug_saved = None
 
 
+class BlockSaved(NamedTuple):
+    """What the block forward leaves for its backward besides the inputs: the one place that knows the flat tensor order
+    (``save_for_backward``, the output list of ``torch.ops.diffusion_net.block``) and that fills a ``BlockSavedStruct``."""
+    xs: torch.Tensor
+    xd: torch.Tensor
+    words: torch.Tensor      # [magnitude words of the saved activations | max |out|]
+    feats: list              # gx, gy, g, bre, bim with gradient features, else empty
+    hs: list                 # post-ReLU hidden activations of the MiniMLP
+
+    def flat(self):
+        return [self.xs, self.xd, self.words, *self.feats, *self.hs]
+
+    @classmethod
+    def from_flat(cls, cfg, ts):
+        n_feat = 5 if cfg.with_grad else 0
+        return cls(ts[0], ts[1], ts[2], list(ts[3:3 + n_feat]), list(ts[3 + n_feat:]))
+
+    def struct(self):
+        sv = _hip.BlockSavedStruct()
+        sv.xs, sv.xd = self.xs.data_ptr(), self.xd.data_ptr()
+        if self.feats:
+            sv.gx, sv.gy, sv.g, sv.bre, sv.bim = (t.data_ptr() for t in self.feats)
+        for i, h in enumerate(self.hs):
+            sv.h[i] = h.data_ptr()
+        sv.amax = self.words.data_ptr()
+        return sv
+
+    def named(self):
+        return {"xs": self.xs, "xd": self.xd, **dict(zip(("gx", "gy", "g", "bre", "bim"), self.feats)), "h": list(self.hs), "words": self.words}
+
+
+def block_fwd(mb, cfg, masks, x, time, A_re, A_im, Ws, bs, x_amax=None, save=True, clamp=False):
+    """-> (out, BlockSaved | None, out_amax | None).  ``save``: the training forward, which writes what the backward needs; ``clamp``:
+    clamp ``time`` to >= 1e-8 in place inside the first launch."""
+    L = _hip.lib()
+    V, Cc = x.shape[0], cfg.C
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
+    # magnitude words of the split-fp16 engine (dn_api.hip): the input's (``x_amax``) travels with the tensor from the block that produced it,
+    # this block's output gets one for the next block; a tensor without one is measured by the library (one extra pass).
+    # words = [saved-activation words | max |out|].  Uninitialised on purpose (a fill per block and step is a launch): a call that tracks
+    # magnitudes zeroes and writes them itself; one that does not leaves them alone, and then nothing reads them -- ``out_amax`` is handed
+    # back, and the backward reads the words, only where dn_block_tracks_amax says so (ADVICE r3)
+    words = new(_hip.BLOCK_AMAX_WORDS + 1)
+    out_amax = words[_hip.BLOCK_AMAX_WORDS:]
+    p = _params_struct(cfg, time, A_re, A_im, Ws, bs, masks, x_amax, out_amax)
+    p.clamp_time = int(clamp)
+    out = new(V, Cc)
+    saved = sv = None
+    if save:
+        saved = BlockSaved(new(mb.n_mesh, mb.k_eig, Cc), new(V, Cc), words, [new(V, Cc) for _ in range(5)] if cfg.with_grad else [],
+                           [new(V, cfg.widths[i + 1]) for i in range(cfg.n_mlp - 1)])
+        sv = saved.struct()
+    ws, n = _ws(mb, L.dn_block_fwd_workspace_bytes(mb.ref(), C.byref(p), int(save)))
+    _hip.check(L.dn_block_fwd_f32(mb.ref(), C.byref(p), x.data_ptr(), out.data_ptr(), C.byref(sv) if save else None, ws.data_ptr(), n,
+                                  _hip.stream_of(x)), "dn_block_fwd_f32")
+    return out, saved, (out_amax if L.dn_block_tracks_amax(mb.ref(), C.byref(p), int(save)) else None)
+
+
+def block_bwd(mb, cfg, masks, d_out, x, time, A_re, A_im, Ws, bs, saved, grads, d_out_amax=None):
+    """grads: the caller's output buffers [d_time, dA_re | None, dA_im | None, dW_0, db_0, dW_1, ...] -> (d_x, d_x_amax | None)"""
+    L = _hip.lib()
+    p = _params_struct(cfg, time, A_re, A_im, Ws, bs, masks)
+    sv, gr = saved.struct(), _hip.BlockGradsStruct()
+    d_x = torch.empty_like(x)
+    dx_amax = torch.empty(1, dtype=torch.float32, device=d_x.device)      # (written only, and returned only, when the call tracks magnitudes)
+    gr.d_x, gr.d_time, gr.dA_re, gr.dA_im = d_x.data_ptr(), grads[0].data_ptr(), _hip.ptr(grads[1]), _hip.ptr(grads[2])
+    gr.d_out_amax, gr.d_x_amax = _hip.ptr(d_out_amax), dx_amax.data_ptr()
+    for i in range(cfg.n_mlp):
+        gr.dW[i], gr.db[i] = grads[3 + 2 * i].data_ptr(), grads[4 + 2 * i].data_ptr()
+    ws, n = _ws(mb, L.dn_block_bwd_workspace_bytes(mb.ref(), C.byref(p)))
+    _hip.check(L.dn_block_bwd_f32(mb.ref(), C.byref(p), x.data_ptr(), C.byref(sv), d_out.data_ptr(), C.byref(gr),
+                                  ws.data_ptr(), n, _hip.stream_of(d_out)), "dn_block_bwd_f32")
+    return d_x, (dx_amax if L.dn_block_tracks_amax(mb.ref(), C.byref(p), 2) else None)
+
+
 class BlockFn(torch.autograd.Function):
-    """forward(x, time, A_re, A_im, *W_and_b) with non-tensor (mb, cfg, masks) first."""
+    """forward(x, time, A_re, A_im, *W_and_b) with non-tensor (mb, cfg, masks, grad_enabled) first."""
 
     @staticmethod
     @_on_device
-    def forward(ctx, mb, cfg, masks, x, time, A_re, A_im, *wb):
+    def forward(ctx, mb, cfg, masks, grad_enabled, x, time, A_re, A_im, *wb):
         _require(x, mb)
         ctx.sinks = _sinks([time, A_re, A_im, *wb])
-        L = _hip.lib()
         time_param = time
         x, time = _f32c(x), _f32c(time)
-        # (the torch.library form of this op must not write to an input it does not declare as mutated: layers.py clamps before it, torchlib.py
-        # sets ctx.no_clamp)
-        clamp_in_call = bool(getattr(cfg, "clamp_time", False)) and not getattr(ctx, "no_clamp", False)
-        if clamp_in_call and time.data_ptr() != time_param.data_ptr():     # a converted copy: the library would clamp the copy, not the Parameter
+        clamp = cfg.clamp_time
+        if clamp and time.data_ptr() != time_param.data_ptr():     # a converted copy: the library would clamp the copy, not the Parameter
             time_param.data.clamp_(min=1e-8)
-            time, clamp_in_call = _f32c(time_param), False
+            time, clamp = _f32c(time_param), False
         A_re = _f32c(A_re) if A_re is not None else None
         A_im = _f32c(A_im) if A_im is not None else None
         Ws = [_f32c(w) for w in wb[0::2]]
         bs = [_f32c(b) for b in wb[1::2]]
-        dev, V, Cc = x.device, x.shape[0], cfg.C
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        # magnitude words of the split-fp16 engine (dn_api.hip): the input's travels with the tensor from the block that produced it,
-        # this block's output gets one for the next block; a tensor without one is measured by the library (one extra pass)
-        x_amax = _amax_of(x)
-        # [saved-activation words | max |out|].  Uninitialised on purpose (a fill per block and step is a launch): a call that tracks
-        # magnitudes zeroes and writes them itself; one that does not leaves them alone, and then nothing reads them -- the tag below and the
-        # backward's use are both conditional on dn_block_tracks_amax (ADVICE r3)
-        words = new(_hip.BLOCK_AMAX_WORDS + 1)
-        out_amax = words[_hip.BLOCK_AMAX_WORDS:]
-        p = _params_struct(cfg, time, A_re, A_im, Ws, bs, masks, x_amax, out_amax)
-        p.clamp_time = 1 if clamp_in_call else 0
-        out = new(V, Cc)
         # ctx.needs_input_grad is True for every Parameter even under torch.no_grad() (torch 2.10), and grad mode is always off inside a
-        # Function's forward: the caller samples torch.is_grad_enabled() and leaves it on the config (layers.forward_packed).  Until round 6
-        # every "inference" call through the package ran the TRAINING forward (eight saved arrays of [V, C] written per block: +11 % at
-        # BASELINE config 4's shape) -- and with it never took the inference-only kernel choices.
-        need_grad = any(ctx.needs_input_grad) and bool(getattr(cfg, "_grad_enabled", True))
-        if need_grad:
-            sv = _hip.BlockSavedStruct()
-            xs, xd = new(mb.n_mesh, mb.k_eig, Cc), new(V, Cc)
-            feats = [new(V, Cc) for _ in range(5)] if cfg.with_grad else []
-            hs = [new(V, cfg.widths[i + 1]) for i in range(cfg.n_mlp - 1)]
-            sv.xs, sv.xd = xs.data_ptr(), xd.data_ptr()
-            if cfg.with_grad:
-                sv.gx, sv.gy, sv.g, sv.bre, sv.bim = (t.data_ptr() for t in feats)
-            for i, h in enumerate(hs):
-                sv.h[i] = h.data_ptr()
-            sv.amax = words.data_ptr()
-            sv_ref = C.byref(sv)
-        else:
-            sv_ref = None
-        ws, n = _ws(mb, L.dn_block_fwd_workspace_bytes(mb.ref(), C.byref(p), int(need_grad)))
-        _hip.check(L.dn_block_fwd_f32(mb.ref(), C.byref(p), x.data_ptr(), out.data_ptr(), sv_ref, ws.data_ptr(), n,
-                                      _hip.stream_of(x)), "dn_block_fwd_f32")
+        # Function's forward: the caller samples torch.is_grad_enabled() and passes it as ``grad_enabled`` (layers.forward_packed).  Until
+        # round 6 every "inference" call through the package ran the TRAINING forward (eight saved arrays of [V, C] written per block: +11 %
+        # at BASELINE config 4's shape) -- and with it never took the inference-only kernel choices.
+        need_grad = any(ctx.needs_input_grad) and grad_enabled
+        out, saved, out_amax = block_fwd(mb, cfg, masks, x, time, A_re, A_im, Ws, bs, _amax_of(x), need_grad, clamp)
         if need_grad:
             ctx.mb, ctx.cfg, ctx.masks = mb, cfg, masks
-            ctx.n_feat, ctx.n_h = len(feats), len(hs)
             ctx.has = (A_re is not None, A_im is not None)
-            ctx.save_for_backward(x, time, xs, xd, words, *feats, *hs, *Ws, *bs,
-                                  *([A_re] if A_re is not None else []), *([A_im] if A_im is not None else []))
+            ctx.save_for_backward(x, time, *Ws, *bs, *saved.flat(), *(t for t in (A_re, A_im) if t is not None))
             if debug_saved is not None:
-                debug_saved.append({"xs": xs, "xd": xd, **dict(zip(("gx", "gy", "g", "bre", "bim"), feats)), "h": list(hs), "words": words})
-        if L.dn_block_tracks_amax(mb.ref(), C.byref(p), 1 if need_grad else 0):
-            _tag_amax(out, out_amax)  # the next block reads it off its input (a call that does not track magnitudes leaves the word alone: no tag)
-        return out
+                debug_saved.append(saved.named())
+        return _tag_amax(out, out_amax)  # the next block reads it off its input (a call that does not track magnitudes leaves the word alone: no tag)
 
     @staticmethod
     @_on_device
     def backward(ctx, d_out):
-        L = _hip.lib()
         mb, cfg, masks = ctx.mb, ctx.cfg, ctx.masks
-        pre = getattr(cfg, "grad_pre_hook", None)
-        if pre is not None:
-            pre()
-        sav = list(ctx.saved_tensors)
-        x, time, xs, xd, words = sav[:5]
-        pos = 5
-        feats = sav[pos:pos + ctx.n_feat]; pos += ctx.n_feat
-        hs = sav[pos:pos + ctx.n_h]; pos += ctx.n_h
-        Ws = sav[pos:pos + cfg.n_mlp]; pos += cfg.n_mlp
-        bs = sav[pos:pos + cfg.n_mlp]; pos += cfg.n_mlp
-        A_re = A_im = None
-        if ctx.has[0]:
-            A_re = sav[pos]; pos += 1
-        if ctx.has[1]:
-            A_im = sav[pos]; pos += 1
+        if cfg.grad_pre_hook is not None:
+            cfg.grad_pre_hook()
+        sav, n = list(ctx.saved_tensors), cfg.n_mlp
+        A_im = sav.pop() if ctx.has[1] else None
+        A_re = sav.pop() if ctx.has[0] else None
+        x, time, Ws, bs = sav[0], sav[1], sav[2:2 + n], sav[2 + n:2 + 2 * n]
         d_out = _f32c(d_out)
-        p = _params_struct(cfg, time, A_re, A_im, Ws, bs, masks)
-        sv = _hip.BlockSavedStruct()
-        sv.xs, sv.xd = xs.data_ptr(), xd.data_ptr()
-        if cfg.with_grad:
-            sv.gx, sv.gy, sv.g, sv.bre, sv.bim = (t.data_ptr() for t in feats)
-        for i, h in enumerate(hs):
-            sv.h[i] = h.data_ptr()
-        sv.amax = words.data_ptr()
-        gr = _hip.BlockGradsStruct()
-        sk = ctx.sinks                # order: time, A_re, A_im, W0, b0, W1, b1, ...
-        d_x, d_time = torch.empty_like(x), _grad_out(sk[0], time)
-        dA_re, dA_im = _grad_out(sk[1], A_re), _grad_out(sk[2], A_im)
-        dWs = [_grad_out(sk[3 + 2 * i], w) for i, w in enumerate(Ws)]
-        dbs = [_grad_out(sk[4 + 2 * i], b) for i, b in enumerate(bs)]
-        gr.d_x, gr.d_time, gr.dA_re, gr.dA_im = d_x.data_ptr(), d_time.data_ptr(), _hip.ptr(dA_re), _hip.ptr(dA_im)
-        dx_amax = torch.empty(1, dtype=torch.float32, device=d_x.device)      # (written only, and tagged only, when the call tracks magnitudes)
-        gr.d_out_amax, gr.d_x_amax = _hip.ptr(_amax_of(d_out)), dx_amax.data_ptr()
-        for i in range(cfg.n_mlp):
-            gr.dW[i], gr.db[i] = dWs[i].data_ptr(), dbs[i].data_ptr()
-        ws, n = _ws(mb, L.dn_block_bwd_workspace_bytes(mb.ref(), C.byref(p)))
-        _hip.check(L.dn_block_bwd_f32(mb.ref(), C.byref(p), x.data_ptr(), C.byref(sv), d_out.data_ptr(), C.byref(gr),
-                                      ws.data_ptr(), n, _hip.stream_of(d_out)), "dn_block_bwd_f32")
-        wb = []
-        for dw, db in zip(dWs, dbs):
-            wb += [dw, db]
-        d_time, dA_re, dA_im, *wb = _deliver(ctx.sinks, [d_time, dA_re, dA_im, *wb])
-        hook = getattr(cfg, "grad_hook", None)
-        if hook is not None:          # dist.FlatParams: this block's gradient range may go out now
-            hook()
-        if L.dn_block_tracks_amax(mb.ref(), C.byref(p), 2):
-            _tag_amax(d_x, dx_amax)   # the block before this one finds it on the gradient it receives
-        return (None, None, None, d_x, d_time, dA_re, dA_im, *wb)
+        likes = [time, A_re, A_im]
+        for w, b in zip(Ws, bs):
+            likes += [w, b]
+        grads = [_grad_out(s, t) for s, t in zip(ctx.sinks, likes)]      # order: time, A_re, A_im, W0, b0, W1, b1, ...
+        d_x, dx_amax = block_bwd(mb, cfg, masks, d_out, x, time, A_re, A_im, Ws, bs, BlockSaved.from_flat(cfg, sav[2 + 2 * n:]), grads,
+                                 _amax_of(d_out))
+        grads = _deliver(ctx.sinks, grads)
+        if cfg.grad_hook is not None:          # dist.FlatParams: this block's gradient range may go out now
+            cfg.grad_hook()
+        # (the tag: the block before this one finds it on the gradient it receives)
+        return (None, None, None, None, _tag_amax(d_x, dx_amax), *grads)
 
 
 # ----------------------------------------------------------------------------------------------
 # output remaps (layers.py:379-397)
 # ----------------------------------------------------------------------------------------------
+def _csr_mean(x, rowptr, col, n_out, n_per):
+    out = torch.empty(n_out, x.shape[1], dtype=torch.float32, device=x.device)
+    _hip.check(_hip.lib().dn_csr_mean_f32(rowptr.data_ptr(), col.data_ptr(), n_out, x.data_ptr(), x.shape[1], float(n_per), out.data_ptr(),
+                                          _hip.stream_of(x)), "dn_csr_mean_f32")
+    return out
+
+
+def gather_mean_fwd(x, pat: GatherPattern):
+    return _csr_mean(x, pat.rowptr, pat.col, pat.n_out, pat.n_per)
+
+
+def gather_mean_bwd(d_out, pat: GatherPattern):
+    return _csr_mean(d_out, pat.t_rowptr, pat.t_col, pat.n_src, pat.n_per)
+
+
 class GatherMeanFn(torch.autograd.Function):
     """out[i] = mean_j x[index[i, j]]  (faces: 3 rows, edges: 2 rows)"""
 
@@ -519,23 +550,29 @@ class GatherMeanFn(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, pat: GatherPattern):
         _require(x)
-        x = _f32c(x)
-        out = torch.empty(pat.n_out, x.shape[1], dtype=torch.float32, device=x.device)
-        _hip.check(_hip.lib().dn_csr_mean_f32(pat.rowptr.data_ptr(), pat.col.data_ptr(), pat.n_out, x.data_ptr(), x.shape[1],
-                                              float(pat.n_per), out.data_ptr(), _hip.stream_of(x)), "dn_csr_mean_f32")
         ctx.pat = pat
-        return out
+        return gather_mean_fwd(_f32c(x), pat)
 
     @staticmethod
     @_on_device
     def backward(ctx, d_out):
-        pat = ctx.pat
-        d_out = _f32c(d_out)
-        d_x = torch.empty(pat.n_src, d_out.shape[1], dtype=torch.float32, device=d_out.device)
-        _hip.check(_hip.lib().dn_csr_mean_f32(pat.t_rowptr.data_ptr(), pat.t_col.data_ptr(), pat.n_src, d_out.data_ptr(),
-                                              d_out.shape[1], float(pat.n_per), d_x.data_ptr(), _hip.stream_of(d_out)),
-                   "dn_csr_mean_f32")
-        return d_x, None
+        return gather_mean_bwd(_f32c(d_out), ctx.pat), None
+
+
+def mass_mean_fwd(mb, x):
+    """-> (out, msum): the per-mesh mass sums are what the backward needs"""
+    out = torch.empty(mb.n_mesh, x.shape[1], dtype=torch.float32, device=x.device)
+    msum = torch.empty(mb.n_mesh, dtype=torch.float32, device=x.device)
+    _hip.check(_hip.lib().dn_mass_mean_fwd_f32(mb.ref(), x.data_ptr(), x.shape[1], out.data_ptr(), msum.data_ptr(),
+                                               _hip.stream_of(x)), "dn_mass_mean_fwd_f32")
+    return out, msum
+
+
+def mass_mean_bwd(mb, msum, d_out):
+    d_x = torch.empty(mb.v_total, d_out.shape[1], dtype=torch.float32, device=d_out.device)
+    _hip.check(_hip.lib().dn_mass_mean_bwd_f32(mb.ref(), msum.data_ptr(), d_out.data_ptr(), d_out.shape[1],
+                                               d_x.data_ptr(), _hip.stream_of(d_out)), "dn_mass_mean_bwd_f32")
+    return d_x
 
 
 class MassMeanFn(torch.autograd.Function):
@@ -545,11 +582,7 @@ class MassMeanFn(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, mb):
         _require(x, mb)
-        x = _f32c(x)
-        out = torch.empty(mb.n_mesh, x.shape[1], dtype=torch.float32, device=x.device)
-        msum = torch.empty(mb.n_mesh, dtype=torch.float32, device=x.device)
-        _hip.check(_hip.lib().dn_mass_mean_fwd_f32(mb.ref(), x.data_ptr(), x.shape[1], out.data_ptr(), msum.data_ptr(),
-                                                   _hip.stream_of(x)), "dn_mass_mean_fwd_f32")
+        out, msum = mass_mean_fwd(mb, _f32c(x))
         ctx.mb = mb
         ctx.save_for_backward(msum)
         return out
@@ -557,17 +590,49 @@ class MassMeanFn(torch.autograd.Function):
     @staticmethod
     @_on_device
     def backward(ctx, d_out):
-        (msum,) = ctx.saved_tensors
-        d_out = _f32c(d_out)
-        d_x = torch.empty(ctx.mb.v_total, d_out.shape[1], dtype=torch.float32, device=d_out.device)
-        _hip.check(_hip.lib().dn_mass_mean_bwd_f32(ctx.mb.ref(), msum.data_ptr(), d_out.data_ptr(), d_out.shape[1],
-                                                   d_x.data_ptr(), _hip.stream_of(d_out)), "dn_mass_mean_bwd_f32")
-        return d_x, None
+        return mass_mean_bwd(ctx.mb, ctx.saved_tensors[0], _f32c(d_out)), None
 
 
 # ----------------------------------------------------------------------------------------------
 # the head on the far side of the path (dn_head.hip): [gather-mean] -> [log_softmax] -> log-probabilities -> [NLL / smoothed loss]
 # ----------------------------------------------------------------------------------------------
+def head_fwd(x, pat, labels, log_softmax, smoothing, need_logp):
+    """-> (logp | None, loss | None, count | None, labels as the kernel read them: flat int64 | None)"""
+    L = _hip.lib()
+    n_src, Cc = x.shape
+    if Cc > _hip.HEAD_MAX_CLASSES:
+        raise ValueError("the fused head handles up to %d classes (got %d); DiffusionNet.forward_packed composes the remap and the "
+                         "activation from separate ops above that" % (_hip.HEAD_MAX_CLASSES, Cc))
+    n_out = pat.n_out if pat is not None else n_src
+    if labels is not None:
+        if labels.dtype != torch.int64:
+            raise TypeError("labels must be int64")
+        labels = labels.reshape(-1).contiguous()
+        if labels.numel() != n_out:
+            raise ValueError("expected %d labels, got %d" % (n_out, labels.numel()))
+    logp = torch.empty(n_out, Cc, dtype=torch.float32, device=x.device) if need_logp else None
+    loss = torch.empty((), dtype=torch.float32, device=x.device) if labels is not None else None
+    count = torch.empty((), dtype=torch.float32, device=x.device) if labels is not None else None
+    ws = _hip.workspace(x.device, L.dn_head_workspace_bytes())
+    _hip.check(L.dn_head_fwd_f32(x.data_ptr(), n_src, Cc, _hip.ptr(pat.rowptr) if pat is not None else None,
+                                 _hip.ptr(pat.col) if pat is not None else None, n_out, float(pat.n_per) if pat is not None else 1.0,
+                                 int(bool(log_softmax)), _hip.ptr(labels), float(smoothing), _hip.ptr(logp), _hip.ptr(loss), _hip.ptr(count),
+                                 ws.data_ptr(), ws.numel(), _hip.stream_of(x)), "dn_head_fwd_f32")
+    return logp, loss, count, labels
+
+
+def head_bwd(pat, log_softmax, smoothing, shape, logp, labels, count, d_logp, d_loss):
+    """shape: (n_src, n_out, classes); any combination of incoming d_logp / d_loss -> d_x"""
+    n_src, n_out, Cc = shape
+    ref = d_logp if d_logp is not None else d_loss
+    d_x = torch.empty(n_src, Cc, dtype=torch.float32, device=ref.device)
+    _hip.check(_hip.lib().dn_head_bwd_f32(_hip.ptr(logp), n_out, Cc, _hip.ptr(pat.t_rowptr) if pat is not None else None,
+                                          _hip.ptr(pat.t_col) if pat is not None else None, n_src, float(pat.n_per) if pat is not None else 1.0,
+                                          int(log_softmax), _hip.ptr(labels) if d_loss is not None else None, float(smoothing), _hip.ptr(d_logp),
+                                          _hip.ptr(d_loss), _hip.ptr(count), d_x.data_ptr(), _hip.stream_of(ref)), "dn_head_bwd_f32")
+    return d_x
+
+
 class HeadFn(torch.autograd.Function):
     """forward(x, pat, labels, log_softmax, smoothing, want_logp) -> (logp or None, loss or None)
 
@@ -579,31 +644,11 @@ class HeadFn(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, pat, labels, log_softmax, smoothing, want_logp):
         _require(x)
-        L = _hip.lib()
-        x = _f32c(x)
-        n_src, Cc = x.shape
-        if Cc > _hip.HEAD_MAX_CLASSES:
-            raise ValueError("the fused head handles up to %d classes (got %d); DiffusionNet.forward_packed composes the remap and the "
-                             "activation from separate ops above that" % (_hip.HEAD_MAX_CLASSES, Cc))
-        n_out = pat.n_out if pat is not None else n_src
-        if labels is not None:
-            if labels.dtype != torch.int64:
-                raise TypeError("labels must be int64")
-            labels = labels.reshape(-1).contiguous()
-            if labels.numel() != n_out:
-                raise ValueError("expected %d labels, got %d" % (n_out, labels.numel()))
         need_logp = want_logp or (log_softmax and ctx.needs_input_grad[0])   # the backward of log_softmax needs the probabilities
-        logp = torch.empty(n_out, Cc, dtype=torch.float32, device=x.device) if need_logp else None
-        loss = torch.empty((), dtype=torch.float32, device=x.device) if labels is not None else None
-        count = torch.empty((), dtype=torch.float32, device=x.device) if labels is not None else None
-        ws = _hip.workspace(x.device, L.dn_head_workspace_bytes())
-        _hip.check(L.dn_head_fwd_f32(x.data_ptr(), n_src, Cc, _hip.ptr(pat.rowptr) if pat is not None else None,
-                                     _hip.ptr(pat.col) if pat is not None else None, n_out, float(pat.n_per) if pat is not None else 1.0,
-                                     int(bool(log_softmax)), _hip.ptr(labels), float(smoothing), _hip.ptr(logp), _hip.ptr(loss), _hip.ptr(count),
-                                     ws.data_ptr(), ws.numel(), _hip.stream_of(x)), "dn_head_fwd_f32")
-        ctx.pat, ctx.lsm, ctx.smoothing, ctx.shape = pat, bool(log_softmax), float(smoothing), (n_src, n_out, Cc)
-        ctx.save_for_backward(*[t for t in (logp, labels, count) if t is not None])
+        logp, loss, count, labels = head_fwd(_f32c(x), pat, labels, log_softmax, smoothing, need_logp)
+        ctx.args = (pat, bool(log_softmax), float(smoothing), (x.shape[0], pat.n_out if pat is not None else x.shape[0], x.shape[1]))
         ctx.has = (logp is not None, labels is not None)
+        ctx.save_for_backward(*[t for t in (logp, labels, count) if t is not None])
         return (logp if want_logp else None), loss
 
     @staticmethod
@@ -611,16 +656,7 @@ class HeadFn(torch.autograd.Function):
     def backward(ctx, d_logp, d_loss):
         sav = list(ctx.saved_tensors)
         logp = sav.pop(0) if ctx.has[0] else None
-        labels = sav.pop(0) if ctx.has[1] else None
-        count = sav.pop(0) if ctx.has[1] else None
-        n_src, n_out, Cc = ctx.shape
-        pat = ctx.pat
-        ref = d_logp if d_logp is not None else d_loss
-        d_x = torch.empty(n_src, Cc, dtype=torch.float32, device=ref.device)
+        labels, count = sav if ctx.has[1] else (None, None)
         d_logp = _f32c(d_logp) if d_logp is not None else None
         d_loss = _f32c(d_loss) if d_loss is not None else None
-        _hip.check(_hip.lib().dn_head_bwd_f32(_hip.ptr(logp), n_out, Cc, _hip.ptr(pat.t_rowptr) if pat is not None else None,
-                                              _hip.ptr(pat.t_col) if pat is not None else None, n_src, float(pat.n_per) if pat is not None else 1.0,
-                                              int(ctx.lsm), _hip.ptr(labels) if d_loss is not None else None, ctx.smoothing, _hip.ptr(d_logp),
-                                              _hip.ptr(d_loss), _hip.ptr(count), d_x.data_ptr(), _hip.stream_of(ref)), "dn_head_bwd_f32")
-        return d_x, None, None, None, None, None
+        return head_bwd(*ctx.args, logp, labels, count, d_logp, d_loss), None, None, None, None, None

@@ -5,9 +5,10 @@ The eager path calls the ``torch.autograd.Function``s of ``ops.py`` directly.  T
 into the ctypes calls or break the graph around them.  Here every op of the packed forward is ALSO registered as a custom operator
 (``torch.ops.diffusion_net.*``) with a fake (meta) kernel and an autograd formula whose backward is itself a registered op, so that a
 compiled ``DiffusionNet.forward_packed`` is one graph with the ops as opaque nodes (``tests/test_gpu_parity.py::
-test_torch_compile_packed_forward``: ``fullgraph=True``).  The implementations are the SAME code: each custom op runs the
-forward / backward of the matching ``ops.*Fn`` on a stand-in context.  ``layers.py`` routes through these ops only while a compiler is
-tracing (``torch.compiler.is_compiling()``); eager execution keeps its direct path (gradient sinks, dist hooks, magnitude tags).
+test_torch_compile_packed_forward``: ``fullgraph=True``).  The implementations are the SAME code: each custom op calls the
+plain launch function (``ops.*_fwd`` / ``ops.*_bwd``) that the matching ``ops.*Fn`` wraps.  ``layers.py`` routes through these ops only
+while a compiler is tracing (``torch.compiler.is_compiling()``); eager execution keeps its direct path (gradient sinks, dist hooks).  The
+magnitude tags of ``ops._tag_amax`` travel here too, wherever the tensor object an op returned is the one the next op receives.
 
 Non-tensor operands travel as integer handles into a weak registry (the caller owns the objects, as with the eager path).  The eager
 autograd formulas pin the objects their backward looks up for as long as the autograd node lives (``_hold``); a COMPILED graph calls the
@@ -22,7 +23,7 @@ from typing import List, Optional
 
 import torch
 from torch import Tensor
-from torch.library import custom_op
+from torch.library import custom_op, infer_schema
 
 from . import _hip, ops
 import weakref
@@ -45,25 +46,29 @@ def _hold(ctx, *handles):
                 _unpin(k)
 
 
-class _Ctx:
-    """What the Functions of ops.py use of an autograd context."""
-
-    def __init__(self, needs):
-        self.needs_input_grad = tuple(needs)
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts
+def _op(name):
+    """A custom operator that mutates no argument and runs with its tensors' device current, as the eager Functions do."""
+    return lambda fn: custom_op(name, mutates_args=(), schema=infer_schema(fn, mutates_args=()))(ops._on_device(fn))
 
 
 def _e(like: Tensor) -> Tensor:
     return like.new_empty(0)
 
 
+def _c(t: Optional[Tensor]) -> Optional[Tensor]:
+    return ops._f32c(t) if t is not None else None
+
+
+def _in(x: Tensor, mb=None) -> Tensor:
+    """The checks and conversions the eager Functions make on their leading operand."""
+    ops._require(x, mb)
+    return _c(x)
+
+
 # ------------------------------------------------------------------------------------------------ nn.Linear on the row axis
-@custom_op("diffusion_net::linear", mutates_args=())
+@_op("diffusion_net::linear")
 def linear(x: Tensor, W: Tensor, b: Tensor, mb: int) -> Tensor:
-    return ops.LinearFn.forward(_Ctx((True, True, True, False)), x, W, b, _obj(mb))
+    return ops._tag_amax(*ops.linear_fwd(_obj(mb), _in(x, _obj(mb)), _c(W), _c(b)))
 
 
 @linear.register_fake
@@ -71,12 +76,10 @@ def _(x, W, b, mb):
     return x.new_empty(x.shape[0], W.shape[0])
 
 
-@custom_op("diffusion_net::linear_bwd", mutates_args=())
+@_op("diffusion_net::linear_bwd")
 def linear_bwd(d_out: Tensor, x: Tensor, W: Tensor, mb: int) -> List[Tensor]:
-    ctx = _Ctx((True, True, True, False))
-    ctx.sinks, ctx.mb, ctx.saved_tensors = [None, None], _obj(mb), (x, W)
-    d_x, dW, db, _ = ops.LinearFn.backward(ctx, d_out)
-    return [d_x, dW, db]
+    dW, db = torch.empty_like(W), W.new_empty(W.shape[0])
+    return [ops._tag_amax(*ops.linear_bwd(_obj(mb), _c(d_out), x, W, dW, db)), dW, db]
 
 
 @linear_bwd.register_fake
@@ -107,15 +110,16 @@ def _masks(seed: int, seed_dev: Optional[Tensor]):
     return (seed, seed_dev) if seed_dev is not None else seed
 
 
-@custom_op("diffusion_net::block", mutates_args=())
+@_op("diffusion_net::block")
 def block(x: Tensor, time: Tensor, A_re: Optional[Tensor], A_im: Optional[Tensor], wb: List[Tensor], mb: int, cfg: int, seed: int,
           seed_dev: Optional[Tensor], n_mesh: int, k_eig: int) -> List[Tensor]:
     """-> [out, xs, xd, words, (gx, gy, g, bre, bim), h_0 ...]: the output and what the backward needs besides the inputs."""
-    ctx = _Ctx([False] * 3 + [True] * (4 + len(wb)))
-    ctx.no_clamp = True        # `time` is an input of a custom op that declares no mutation: the caller has clamped it (layers.forward_packed)
-    _obj(cfg)._grad_enabled = True      # (this op always returns what its backward op needs)
-    out = ops.BlockFn.forward(ctx, _obj(mb), _obj(cfg), _masks(seed, seed_dev), x, time, A_re, A_im, *wb)
-    return [out] + list(ctx.saved_tensors[2:5 + ctx.n_feat + ctx.n_h])
+    # save on: this op always returns what its backward op needs; clamp off: `time` is an input of a custom op that declares no mutation,
+    # the caller has clamped it (layers.forward_packed)
+    x = _in(x, _obj(mb))
+    out, saved, out_amax = ops.block_fwd(_obj(mb), _obj(cfg), _masks(seed, seed_dev), x, _c(time), _c(A_re), _c(A_im), [_c(w) for w in wb[0::2]],
+                                         [_c(b) for b in wb[1::2]], ops._amax_of(x), save=True, clamp=False)
+    return [ops._tag_amax(out, out_amax)] + saved.flat()
 
 
 @block.register_fake
@@ -129,20 +133,15 @@ def _(x, time, A_re, A_im, wb, mb, cfg, seed, seed_dev, n_mesh, k_eig):
     return outs
 
 
-@custom_op("diffusion_net::block_bwd", mutates_args=())
+@_op("diffusion_net::block_bwd")
 def block_bwd(d_out: Tensor, x: Tensor, time: Tensor, A_re: Optional[Tensor], A_im: Optional[Tensor], wb: List[Tensor], saved: List[Tensor],
               mb: int, cfg: int, seed: int, seed_dev: Optional[Tensor]) -> List[Tensor]:
     """-> [d_x, d_time, dA_re | empty, dA_im | empty, dW_0, db_0, ...]"""
-    c = _obj(cfg)
-    ctx = _Ctx([False] * 3 + [True] * (4 + len(wb)))
-    ctx.mb, ctx.cfg, ctx.masks = _obj(mb), c, _masks(seed, seed_dev)
-    ctx.n_feat, ctx.n_h = (5 if c.with_grad else 0), c.n_mlp - 1
-    ctx.has = (A_re is not None, A_im is not None)
-    ctx.sinks = [None] * (3 + len(wb))
-    ctx.saved_tensors = (x, time, *saved, *wb[0::2], *wb[1::2], *([A_re] if A_re is not None else []), *([A_im] if A_im is not None else []))
-    g = ops.BlockFn.backward(ctx, d_out)          # (None, None, None, d_x, d_time, dA_re, dA_im, *wb)
-    d_x, d_time, dA_re, dA_im = g[3:7]
-    return [d_x, d_time, dA_re if dA_re is not None else _e(x), dA_im if dA_im is not None else _e(x), *g[7:]]
+    c, d_out = _obj(cfg), _c(d_out)
+    grads = [torch.empty_like(t) if t is not None else None for t in (time, A_re, A_im, *wb)]
+    d_x, dx_amax = ops.block_bwd(_obj(mb), c, _masks(seed, seed_dev), d_out, x, time, A_re, A_im, wb[0::2], wb[1::2],
+                                 ops.BlockSaved.from_flat(c, saved), grads, ops._amax_of(d_out))
+    return [ops._tag_amax(d_x, dx_amax)] + [g if g is not None else _e(x) for g in grads]
 
 
 @block_bwd.register_fake
@@ -185,9 +184,9 @@ block.register_autograd(_block_backward, setup_context=_block_setup)
 
 
 # ------------------------------------------------------------------------------------------------ output remaps
-@custom_op("diffusion_net::gather_mean", mutates_args=())
+@_op("diffusion_net::gather_mean")
 def gather_mean(x: Tensor, pat: int, n_out: int) -> Tensor:
-    return ops.GatherMeanFn.forward(_Ctx((True, False)), x, _obj(pat))
+    return ops.gather_mean_fwd(_in(x), _obj(pat))
 
 
 @gather_mean.register_fake
@@ -195,11 +194,9 @@ def _(x, pat, n_out):
     return x.new_empty(n_out, x.shape[1])
 
 
-@custom_op("diffusion_net::gather_mean_bwd", mutates_args=())
+@_op("diffusion_net::gather_mean_bwd")
 def gather_mean_bwd(d_out: Tensor, pat: int, n_src: int) -> Tensor:
-    ctx = _Ctx((True, False))
-    ctx.pat = _obj(pat)
-    return ops.GatherMeanFn.backward(ctx, d_out)[0]
+    return ops.gather_mean_bwd(_c(d_out), _obj(pat))
 
 
 @gather_mean_bwd.register_fake
@@ -215,11 +212,9 @@ def _gm_setup(ctx, inputs, output):
 gather_mean.register_autograd(lambda ctx, g: (gather_mean_bwd(g.contiguous(), ctx.pat, ctx.n_src), None, None), setup_context=_gm_setup)
 
 
-@custom_op("diffusion_net::mass_mean", mutates_args=())
+@_op("diffusion_net::mass_mean")
 def mass_mean(x: Tensor, mb: int, n_mesh: int) -> List[Tensor]:
-    ctx = _Ctx((True, False))
-    out = ops.MassMeanFn.forward(ctx, x, _obj(mb))
-    return [out, ctx.saved_tensors[0]]
+    return list(ops.mass_mean_fwd(_obj(mb), _in(x, _obj(mb))))
 
 
 @mass_mean.register_fake
@@ -227,11 +222,9 @@ def _(x, mb, n_mesh):
     return [x.new_empty(n_mesh, x.shape[1]), x.new_empty(n_mesh)]
 
 
-@custom_op("diffusion_net::mass_mean_bwd", mutates_args=())
+@_op("diffusion_net::mass_mean_bwd")
 def mass_mean_bwd(d_out: Tensor, msum: Tensor, mb: int, v_total: int) -> Tensor:
-    ctx = _Ctx((True, False))
-    ctx.mb, ctx.saved_tensors = _obj(mb), (msum,)
-    return ops.MassMeanFn.backward(ctx, d_out)[0]
+    return ops.mass_mean_bwd(_obj(mb), msum, _c(d_out))
 
 
 @mass_mean_bwd.register_fake
@@ -250,13 +243,11 @@ mass_mean.register_autograd(lambda ctx, grads: (mass_mean_bwd(grads[0].contiguou
 
 
 # ------------------------------------------------------------------------------------------------ fused head (remap + log_softmax + loss)
-@custom_op("diffusion_net::head", mutates_args=())
+@_op("diffusion_net::head")
 def head(x: Tensor, pat: int, labels: Optional[Tensor], log_softmax: bool, smoothing: float, n_out: int) -> List[Tensor]:
     """-> [log-probabilities, loss | empty, valid-row count | empty]"""
-    ctx = _Ctx((True,) + (False,) * 5)
-    logp, loss = ops.HeadFn.forward(ctx, x, _obj(pat), labels, log_softmax, smoothing, True)
-    count = ctx.saved_tensors[-1] if labels is not None else _e(x)
-    return [logp, loss if loss is not None else _e(x), count]
+    logp, loss, count, _ = ops.head_fwd(_in(x), _obj(pat), labels, log_softmax, smoothing, True)
+    return [logp, loss if loss is not None else _e(x), count if count is not None else _e(x)]
 
 
 @head.register_fake
@@ -265,16 +256,11 @@ def _(x, pat, labels, log_softmax, smoothing, n_out):
     return [x.new_empty(n_out, x.shape[1]), sc(), sc()]
 
 
-@custom_op("diffusion_net::head_bwd", mutates_args=())
+@_op("diffusion_net::head_bwd")
 def head_bwd(d_logp: Optional[Tensor], d_loss: Optional[Tensor], logp: Tensor, labels: Optional[Tensor], count: Optional[Tensor], pat: int,
              log_softmax: bool, smoothing: float, n_src: int) -> Tensor:
-    ctx = _Ctx((True,) + (False,) * 5)
-    p = _obj(pat)
-    ctx.pat, ctx.lsm, ctx.smoothing = p, log_softmax, smoothing
-    ctx.shape = (n_src, logp.shape[0], logp.shape[1])
-    ctx.has = (True, labels is not None)
-    ctx.saved_tensors = tuple(t for t in (logp, labels, count) if t is not None)
-    return ops.HeadFn.backward(ctx, d_logp, d_loss)[0]
+    return ops.head_bwd(_obj(pat), log_softmax, smoothing, (n_src, logp.shape[0], logp.shape[1]), logp, labels, count if labels is not None else None,
+                        _c(d_logp), _c(d_loss))
 
 
 @head_bwd.register_fake

@@ -958,6 +958,52 @@ def run_compile(device, sizes=(300, 140), K=16, C=32, seed=8):
                 assert torch.equal(a, b)
 
 
+
+def run_block_config_is_static(device, sizes=(300, 140), K=16, C=32, seed=8):
+    """No call through a block writes to its ``BlockConfig``: grad mode and "do not clamp" reach the launch as arguments, so an inference
+    forward, a training step and the ``torch.library`` form of the op can interleave (or run on replicas that share a config) without
+    steering each other.  ``ops.debug_saved`` shows which forward ran: the inference one saves nothing."""
+    from diffusion_net import torchlib  # noqa: F401  (registers torch.ops.diffusion_net.*)
+    torch.manual_seed(seed)
+    blk = diffusion_net.layers.DiffusionNetBlock(C, [C, C], dropout=False).to(device)
+    with torch.no_grad():
+        blk.diffusion.diffusion_time.uniform_(0.05, 0.5)
+    meshes, _ = make_ragged(sizes, K, 3, seed)
+    mb = pack(meshes, device)
+    x = torch.randn(sum(sizes), C, generator=torch.Generator().manual_seed(seed)).to(device)
+    before = dict(vars(blk._cfg))
+
+    def inference():
+        ops.debug_saved = []
+        try:
+            with torch.no_grad():
+                out = blk.forward_packed(x, mb)
+            assert ops.debug_saved == [], "a no_grad forward saved activations: it ran the training forward"
+        finally:
+            ops.debug_saved = None
+        assert dict(vars(blk._cfg)) == before
+        return out
+
+    first = inference()
+    ops.debug_saved = []
+    try:
+        trained = blk.forward_packed(x, mb)
+        assert len(ops.debug_saved) == 1
+    finally:
+        ops.debug_saved = None
+    trained.square().sum().backward()
+    assert all(p.grad is not None for p in blk.parameters())
+    assert dict(vars(blk._cfg)) == before
+    wb = []
+    for lin in blk.mlp.linears():
+        wb += [lin.weight, lin.bias]
+    A_re, A_im = blk.gradient_features.matrices()
+    outs = torch.ops.diffusion_net.block(x, blk.diffusion.diffusion_time, A_re, A_im, wb, mb.handle, blk._cfg.handle, 0, None, mb.n_mesh, mb.k_eig)
+    assert torch.equal(outs[0], trained)
+    assert dict(vars(blk._cfg)) == before
+    assert torch.equal(inference(), first)
+
+
 def run_head_in_net(device, sizes=(300, 140), K=16, C=32, C_out=8, seed=5, outputs_at="faces"):
     """DiffusionNet.forward_packed_loss (remap + log_softmax + NLL in one kernel each way) against the unfused sequence
     forward_packed -> F.nll_loss on the same network: same log-probabilities, same loss, same parameter gradients."""

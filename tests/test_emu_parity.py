@@ -133,6 +133,11 @@ def test_torch_compile_packed_forward_on_emulator(emu):
     parity_cases.run_compile(emu)
 
 
+def test_block_config_is_static_on_emulator(emu):
+    import parity_cases
+    parity_cases.run_block_config_is_static(emu)
+
+
 def test_real_mesh_pipeline_on_emulator(emu):
     import parity_cases
     parity_cases.run_real_mesh_pipeline(emu)

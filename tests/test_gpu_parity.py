@@ -130,6 +130,11 @@ def test_torch_compile_packed_forward(dev):
     parity_cases.run_compile(dev, sizes=(3000, 1400), K=128, C=128, seed=9)
 
 
+def test_block_config_is_static(dev):
+    import parity_cases
+    parity_cases.run_block_config_is_static(dev)
+
+
 def test_real_mesh_pipeline(dev):
     import parity_cases
     parity_cases.run_real_mesh_pipeline(dev, V=3000, K=64, C=128)
