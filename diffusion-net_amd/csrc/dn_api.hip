@@ -32,19 +32,23 @@ inline int opt(int i) { return g_opt[i].value.load(std::memory_order_relaxed); }
 int dn_opt_chain_nw(void) { return opt(O_CHAIN_NW); }
 
 namespace {
+// Carves 256-byte padded regions from a workspace.  Every entry point that takes one has ONE *_layout function naming its regions: the call runs it
+// on the caller's buffer, its *_workspace_bytes() query on a counting Bump, which only adds the padded sizes up and hands out no memory.
 struct Bump {
-    char* p; size_t left; bool ok;
-    Bump(void* ws, size_t n) : p((char*)ws), left(n), ok(true) {
+    char* p; size_t left, used = 0; bool ok = true; const bool counting;
+    Bump(void* ws, size_t n, bool count_only = false) : p((char*)ws), left(n), counting(count_only) {
         size_t mis = (256 - ((uintptr_t)p & 255)) & 255;
         if (mis > left) { ok = false; left = 0; } else { p += mis; left -= mis; }
     }
     float* f(size_t nfloat) {
         size_t bytes = (nfloat * sizeof(float) + 255) & ~(size_t)255;
-        if (bytes > left) { ok = false; return nullptr; }
+        used += bytes;
+        if (counting || bytes > left) { ok = false; return nullptr; }
         float* r = (float*)p; p += bytes; left -= bytes; return r;
     }
 };
-inline size_t pad256(size_t nfloat) { return ((nfloat * sizeof(float) + 255) & ~(size_t)255); }
+// what a *_workspace_bytes() returns for a layout: its regions + slack for a base that is not 256-byte aligned
+template <class Layout> size_t ws_query(Layout layout) { Bump b(nullptr, 0, true); layout(b); return b.used + 512; }
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline const DnTile* T(const dn_tile_t* t) { return reinterpret_cast<const DnTile*>(t); }
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
@@ -100,21 +104,29 @@ void tn_finish(TnArgs& g) {
 }
 
 // ---- dn_diffuse.hip, for batches that carry a plan, K = C = 128, 16-byte aligned operands.  Option "diffuse":
-//   2 (default)  the back-projection of every diffusion (and of dn_from_basis_f32) is the DIRECT row product launch (bp_ok)
-//   1            the whole operator as one persistent launch (diffuse_ok): correct on any residency, measured slower than the launches on
+//   2 (default)  the back-projection of every diffusion (and of dn_from_basis_f32) is the DIRECT row product launch (DiffuseRoute.direct)
+//   1            the whole operator as one persistent launch (DiffuseRoute.one): correct on any residency, measured slower than the launches on
 //                every batch but many-small-meshes ones -- kept selectable
 //   0            the wave-specialised row GEMM of rounds 1-4
-bool diffuse_ok(const dn_mesh_batch_t* mb, int C) {
-    return opt(O_DIFFUSE) == 1 && mb->df_plan && mb->df_n_wg > 0 && mb->df_n_groups > 0 && mb->df_n_groups <= DN_DF_MAX_GROUPS && mb->k_eig == 128 && C == 128 &&
-           mb->df_n_wg == dn_num_cus() && mb->df_v_total == mb->v_total;
+// DiffuseRoute: how a diffusion (forward, backward, or a back-projection alone) at width C runs on this batch.  Computed ONCE per call from the
+// batch and the options; the size query, the layout and the body read that one value.  What depends on the call's pointers (alignment, operands
+// the caller left out) refines it in the call.
+struct DiffuseRoute {
+    bool one, direct;
+    bool wide;      // the forward back-projection at K = C = 256 as the ring kernel of dn_backproject_wide.hip (3-term engine; option "diffuse" != 0;
+                    // needs a workspace for the split spectrum: the block calls and dn_diffusion_f32 pass one, callers without take the row GEMM)
+};
+DiffuseRoute diffuse_route(const dn_mesh_batch_t* mb, int C) {
+    const int o = opt(O_DIFFUSE);
+    // (the plan is caller data the kernels index memory with: it must have been made for this device's workgroup count and -- the stamp
+    // dn_mesh_batch_t.df_v_total, set by whoever called dn_diffusion_plan() -- for this batch's row count; anything else takes the row GEMM)
+    const bool plan = mb->df_plan && mb->df_n_wg > 0 && mb->k_eig == 128 && C == 128 && mb->df_n_wg == dn_num_cus() && mb->df_v_total == mb->v_total;
+    DiffuseRoute r;
+    r.one = o == 1 && plan && mb->df_n_groups > 0 && mb->df_n_groups <= DN_DF_MAX_GROUPS;
+    r.direct = o != 0 && plan && mb->df_n_groups == 1;
+    r.wide = o != 0 && mb->tiles && dn_backproject_wide_ok(mb->k_eig, C, mb->n_tiles) && al16(mb->evecs);
+    return r;
 }
-// (the plan is caller data the kernels index memory with: it must have been made for this device's workgroup count and -- the stamp
-// dn_mesh_batch_t.df_v_total, set by whoever called dn_diffusion_plan() -- for this batch's row count; anything else takes the row GEMM)
-bool plan_matches(const dn_mesh_batch_t* mb) { return mb->df_n_wg == dn_num_cus() && mb->df_v_total == mb->v_total; }
-bool bp_ok(const dn_mesh_batch_t* mb, int C) {
-    return opt(O_DIFFUSE) != 0 && mb->df_plan && mb->df_n_wg > 0 && mb->df_n_groups == 1 && mb->k_eig == 128 && C == 128 && plan_matches(mb);
-}
-size_t diffuse_ws_floats(const dn_mesh_batch_t* mb) { return dn_diffuse_ws_bytes(mb->df_n_wg, mb->df_n_groups, mb->n_mesh) / sizeof(float); }
 int diffuse_dt_rows(const dn_mesh_batch_t* mb) { return dn_diffuse_dt_rows(mb->df_n_wg, mb->df_n_groups); }
 DfLaunch diffuse_new(const dn_mesh_batch_t* mb, void* ws) {
     DfLaunch L;
@@ -139,16 +151,11 @@ int to_basis_partials(const dn_mesh_batch_t* mb, const float* x, int C, bool use
     tn_finish(g);
     return dn_launch_tngemm(g, mb->n_chunks, st);
 }
-// the forward back-projection at K = C = 256 as the ring kernel of dn_backproject_wide.hip (3-term engine; option "diffuse" != 0; needs a
-// workspace for the split spectrum: the block calls and dn_diffusion_f32 pass one, callers without take the row GEMM)
-bool bw_ok(const dn_mesh_batch_t* mb, int C) {
-    return opt(O_DIFFUSE) != 0 && mb->tiles && dn_backproject_wide_ok(mb->k_eig, C, mb->n_tiles) && al16(mb->evecs);
-}
-int from_basis(const dn_mesh_batch_t* mb, const float* spec, int C, float* out, const float* add, bool mass_epi, hipStream_t st,
+int from_basis(const dn_mesh_batch_t* mb, const DiffuseRoute& r, const float* spec, int C, float* out, const float* add, bool mass_epi, hipStream_t st,
                const F16& f = F16(), float* wide_ws = nullptr) {
-    if (wide_ws && !mass_epi && !add && !f.on && bw_ok(mb, C) && al16(spec) && al16(out) && al16(wide_ws))
+    if (wide_ws && !mass_epi && !add && !f.on && r.wide && al16(spec) && al16(out) && al16(wide_ws))
         return dn_launch_backproject_wide(T(mb->tiles), mb->n_tiles, mb->n_mesh, mb->evecs, spec, wide_ws, out, f.o, mb->k_eig, C, mb->v_total, st);
-    if (bp_ok(mb, C) && al16(spec) && al16(out) && al16(add) && al16(mb->evecs))       // direct row product, on the engine f asks for
+    if (r.direct && al16(spec) && al16(out) && al16(add) && al16(mb->evecs))       // direct row product, on the engine f asks for
         return dn_launch_backproject(T(mb->df_plan), mb->df_n_wg, mb->evecs, spec, out, add, mass_epi ? mb->mass : nullptr, f.o, mb->v_total, st,
                                      f.on ? 1 : 0, &f.a, &f.b);
     RgArgs g = rg_new(mb);
@@ -177,19 +184,19 @@ int grad_apply_bwd(const dn_mesh_batch_t* mb, const float* dgx, const float* dgy
     s.x1 = dgx; s.x2 = dgy; s.add = add; s.o1 = dx; s.nrows = mb->v_total; s.C = C; s.ldx = C; s.ldo = C; s.mode = DN_SP_BWD2; s.div = 1.f; s.acct_nnz = mb->g_nnz;
     return dn_launch_spmm(s, st);
 }
+// B operands of the two outputs of a gradient-feature product: [[A_re, s A_im], [-s A_im, A_re]]; A_im null: A_re on the diagonal only
+void rg_rot(RgArgs& g, const float* A_re, const float* A_im, float s) {
+    g.b[0][0] = A_re; g.bsign[0][0] = 1.f;  g.b[0][1] = A_im ? A_im : A_re; g.bsign[0][1] = A_im ? s : 0.f;
+    g.b[1][0] = A_im ? A_im : A_re; g.bsign[1][0] = A_im ? -s : 0.f;  g.b[1][1] = A_re; g.bsign[1][1] = 1.f;
+}
 int gradfeat_fwd(const dn_mesh_batch_t* mb, const float* gx, const float* gy, const float* A_re, const float* A_im, int C,
                  float* g_out, float* bre, float* bim, hipStream_t st, const F16& f = F16()) {
     RgArgs g = rg_new(mb);
     rg_f16(g, f);
     rg_seg(g, gx, nullptr, C, C);
     rg_seg(g, gy, nullptr, C, C);
-    if (A_im) {   // Bre = gx A_re^T - gy A_im^T ; Bim = gx A_im^T + gy A_re^T   (layers.py:122-123)
-        g.b[0][0] = A_re; g.bsign[0][0] = 1.f;  g.b[0][1] = A_im; g.bsign[0][1] = -1.f;
-        g.b[1][0] = A_im; g.bsign[1][0] = 1.f;  g.b[1][1] = A_re; g.bsign[1][1] = 1.f;
-    } else {      // Bre = gx A^T ; Bim = gy A^T                                 (layers.py:125-126)
-        g.b[0][0] = A_re; g.bsign[0][0] = 1.f;  g.b[0][1] = A_re; g.bsign[0][1] = 0.f;
-        g.b[1][0] = A_re; g.bsign[1][0] = 0.f;  g.b[1][1] = A_re; g.bsign[1][1] = 1.f;
-    }
+    // Bre = gx A_re^T - gy A_im^T ; Bim = gx A_im^T + gy A_re^T (layers.py:122-123); without rotations Bre = gx A^T ; Bim = gy A^T (layers.py:125-126)
+    rg_rot(g, A_re, A_im, -1.f);
     g.ldb = C; g.b_colk = 1; g.N = C;
     g.mode = DN_EPI_GRADFEAT; g.r0 = gx; g.r1 = gy; g.ldr = C;
     g.o0 = g_out; g.o1 = bre; g.o2 = bim; g.ldo = C;
@@ -205,13 +212,7 @@ int gradfeat_bwd_inputs(const dn_mesh_batch_t* mb, const float* ddots, const flo
     rg_f16(g, f);
     rg_seg(g, ddots, gx, C, C);   // dBre = d_dots * gx
     rg_seg(g, ddots, gy, C, C);   // dBim = d_dots * gy
-    if (A_im) {
-        g.b[0][0] = A_re; g.bsign[0][0] = 1.f;   g.b[0][1] = A_im; g.bsign[0][1] = 1.f;
-        g.b[1][0] = A_im; g.bsign[1][0] = -1.f;  g.b[1][1] = A_re; g.bsign[1][1] = 1.f;
-    } else {
-        g.b[0][0] = A_re; g.bsign[0][0] = 1.f;   g.b[0][1] = A_re; g.bsign[0][1] = 0.f;
-        g.b[1][0] = A_re; g.bsign[1][0] = 0.f;   g.b[1][1] = A_re; g.bsign[1][1] = 1.f;
-    }
+    rg_rot(g, A_re, A_im, 1.f);
     g.ldb = C; g.b_colk = 0; g.N = C;
     g.mode = DN_EPI_GRADFEAT_BWD; g.r0 = ddots; g.r1 = bre; g.r2 = bim; g.ldr = C;
     g.o0 = dgx; g.o1 = dgy; g.ldo = C;
@@ -318,6 +319,69 @@ bool block_params_ok(const dn_block_params_t* p) {
     const int in0 = (p->with_grad ? 3 : 2) * p->C;
     return p->widths[0] == in0 && p->widths[p->n_mlp] == p->C;
 }
+
+// ---- the diffusion operator (layers.py:210) and its backward: one stage each, called by dn_diffusion_*_f32 and by the block calls
+struct DiffuseWs {
+    float *partial, *spec, *dtp;      // split-V partials [n_chunks, K, C]; the scaled spectrum (backward: its gradient) [n_mesh, K, C]; d_t rows (backward)
+    float *one, *one_dtp;             // route.one: scratch of the persistent launch, and its d_t rows (backward)
+    float* wide;                      // route.wide: the spectrum split into ring pieces (forward, K = C = 256)
+};
+DiffuseWs diffuse_layout(Bump& b, const dn_mesh_batch_t* mb, int C, const DiffuseRoute& r, bool fwd, bool bwd) {
+    DiffuseWs w; memset(&w, 0, sizeof(w));
+    w.partial = b.f((size_t)mb->n_chunks * mb->k_eig * C); w.spec = b.f((size_t)mb->n_mesh * mb->k_eig * C);
+    if (bwd) w.dtp = b.f((size_t)dn_spec_bwd_dt_rows(mb->n_mesh, mb->k_eig) * C);
+    if (r.one) w.one = b.f(dn_diffuse_ws_bytes(mb->df_n_wg, mb->df_n_groups, mb->n_mesh) / sizeof(float));      // (the hybrid form uses both sets)
+    if (r.one && bwd) w.one_dtp = b.f((size_t)diffuse_dt_rows(mb) * C);
+    if (r.wide && fwd) w.wide = b.f(dn_backproject_wide_ws_floats(mb->n_mesh, mb->k_eig, C));
+    return w;
+}
+// one persistent launch (dn_diffuse.hip, both products on the 3-term engine, as the three-launch form runs them by default) when the batch
+// carries its plan and the caller allows it (one_ok: no product asked onto the split-fp16 engine, which that form does not have) -- else
+// projection, spectral step, back-projection.  tob / fromb: engines of the two products, fromb.o receives max |xd| on every route; spec_amax
+// receives max |ys|; ysp, ysa (spectral-gradient form): the spectrum as weight pieces + per-mesh magnitudes INSTEAD of a back-projection
+int diffuse_fwd(const dn_mesh_batch_t* mb, const DiffuseRoute& r, const DiffuseWs& w, const float* x, const float* time, int C, float* xs, float* xd,
+                hipStream_t st, bool one_ok, const F16& tob = F16(), const F16& fromb = F16(), float* spec_amax = nullptr, float* ysp = nullptr,
+                float* ysa = nullptr) {
+    if (r.one && one_ok && diffuse_aligned(x, xd, xs, mb->evecs, time, mb->evals)) {
+        DfLaunch L = diffuse_new(mb, w.one);
+        L.x = x; L.time = time; L.xs = xs; L.out = xd; L.out_amax = fromb.o;
+        return dn_launch_diffuse(L, st);
+    }
+    DN_CHECK(to_basis_partials(mb, x, C, true, w.partial, st, tob));
+    DN_CHECK(dn_launch_spec_fwd(w.partial, mb->mesh_chunk_off, mb->evals, time, xs, w.spec, mb->n_mesh, mb->k_eig, C, st, spec_amax));
+    // (spectral form: no back-projection launch, the chained kernel multiplies [evecs | gradX evecs | gradY evecs] by the spectrum itself)
+    if (ysp) return dn_launch_spec_pieces(w.spec, mb->n_mesh, mb->k_eig, C, reinterpret_cast<uint4*>(ysp), ysa, st);
+    return from_basis(mb, r, w.spec, C, xd, nullptr, false, st, fromb, w.wide);
+}
+// d_x = add + (diffusion backward of d_xd), d_time; add may be null.  defer (block): the d_t rows join these deferred sums, which are launched here
+int diffuse_bwd(const dn_mesh_batch_t* mb, const DiffuseRoute& r, const DiffuseWs& w, const float* d_xd, const float* xs, const float* time, int C,
+                const float* add, float* d_x, float* d_time, hipStream_t st, bool one_ok, const F16& tob = F16(), const F16& fromb = F16(),
+                float* spec_amax = nullptr, MrJobs* defer = nullptr) {
+    const int K = mb->k_eig;
+    auto dt_sum = [&](const float* rows, int n) {
+        if (defer && defer->push(rows, n, C, d_time)) return 0;
+        return dn_launch_reduce(rows, d_time, n, C, C, st);
+    };
+    if (r.one && one_ok && diffuse_aligned(d_xd, d_x, xs, mb->evecs, time, add)) {      // one launch (3-term engine throughout) + the d_t row sum
+        DfLaunch L = diffuse_new(mb, w.one);
+        L.bwd = 1; L.x = d_xd; L.time = time; L.xs = const_cast<float*>(xs); L.out = d_x; L.add = add; L.dt_part = w.one_dtp; L.out_amax = fromb.o;
+        DN_CHECK(dn_launch_diffuse(L, st));
+        DN_CHECK(dt_sum(w.one_dtp, diffuse_dt_rows(mb)));
+        return defer ? dn_launch_multi_reduce(*defer, st) : 0;
+    }
+    DN_CHECK(to_basis_partials(mb, d_xd, C, false, w.partial, st, tob));
+    if (dn_spec_bwd_fused_ok(w.partial, time, xs, w.spec, w.dtp, C)) {
+        // one launch: per-mesh sums of the partials, exp(-lambda t), d_t contributions [mesh, eigenvalue group][C]
+        DN_CHECK(dn_launch_spec_bwd_fused(w.partial, mb->mesh_chunk_off, mb->evals, time, xs, w.spec, w.dtp, mb->n_mesh, K, C, st, spec_amax));
+        DN_CHECK(dt_sum(w.dtp, dn_spec_bwd_dt_rows(mb->n_mesh, K)));
+    } else {
+        DN_CHECK(dn_launch_seg_reduce(w.partial, mb->mesh_chunk_off, mb->n_mesh, 0, w.spec, (long long)K * C, st));
+        DN_CHECK(dn_launch_spec_bwd(w.spec, mb->evals, time, xs, w.dtp, mb->n_mesh, K, C, st, spec_amax));
+        DN_CHECK(dn_launch_reduce(w.dtp, d_time, mb->n_mesh, C, C, st));
+    }
+    if (defer) DN_CHECK(dn_launch_multi_reduce(*defer, st));       // every parameter gradient of the block: one fixed-order reduction launch
+    return from_basis(mb, r, w.spec, C, d_x, add, true, st, fromb);
+}
 }  // namespace
 
 // ---- opt-in per-kernel timing --------------------------------------------------------------
@@ -421,74 +485,41 @@ int dn_diffusion_plan(const int32_t* sizes, int n_mesh, int n_wg, int n_groups, 
 }
 
 // ------------------------------------------------------------------ to_basis / from_basis
+static float* to_basis_layout(Bump& b, const dn_mesh_batch_t* mb, int C) { return b.f((size_t)mb->n_chunks * mb->k_eig * C); }
 size_t dn_to_basis_workspace_bytes(const dn_mesh_batch_t* mb, int C) {
-    return pad256((size_t)mb->n_chunks * mb->k_eig * C) + 512;
+    return ws_query([&](Bump& b) { to_basis_layout(b, mb, C); });
 }
 int dn_to_basis_f32(const dn_mesh_batch_t* mb, const float* x, int C, int use_mass, float* spec, void* ws, size_t ws_bytes,
                     void* stream) {
     Bump b(ws, ws_bytes);
-    float* partial = b.f((size_t)mb->n_chunks * mb->k_eig * C);
+    float* partial = to_basis_layout(b, mb, C);
     if (!b.ok) return DN_ERR_INVALID;
     DN_CHECK(to_basis_partials(mb, x, C, use_mass != 0, partial, S(stream)));
     return dn_launch_spec_fwd(partial, mb->mesh_chunk_off, mb->evals, nullptr, spec, nullptr, mb->n_mesh, mb->k_eig, C, S(stream));
 }
 int dn_from_basis_f32(const dn_mesh_batch_t* mb, const float* spec, int C, int scale_rows_by_mass, float* out, void* stream) {
-    return from_basis(mb, spec, C, out, nullptr, scale_rows_by_mass != 0, S(stream));
+    return from_basis(mb, diffuse_route(mb, C), spec, C, out, nullptr, scale_rows_by_mass != 0, S(stream));
 }
 
 // ------------------------------------------------------------------ learned-time diffusion
-size_t dn_diffusion_workspace_bytes(const dn_mesh_batch_t* mb, int C) {
-    size_t n = pad256((size_t)mb->n_chunks * mb->k_eig * C) + pad256((size_t)mb->n_mesh * mb->k_eig * C) +
-               pad256((size_t)dn_spec_bwd_dt_rows(mb->n_mesh, mb->k_eig) * C) + 512;
-    if (diffuse_ok(mb, C)) n += pad256(diffuse_ws_floats(mb)) + pad256((size_t)diffuse_dt_rows(mb) * C);      // (the hybrid form uses both sets)
-    if (bw_ok(mb, C)) n += pad256(dn_backproject_wide_ws_floats(mb->n_mesh, mb->k_eig, C));                   // (K = C = 256: the split spectrum)
-    return n;
+size_t dn_diffusion_workspace_bytes(const dn_mesh_batch_t* mb, int C) {      // one query for both directions: the union of their regions
+    return ws_query([&](Bump& b) { diffuse_layout(b, mb, C, diffuse_route(mb, C), true, true); });
 }
 int dn_diffusion_fwd_f32(const dn_mesh_batch_t* mb, const float* x, const float* time, int C, float* xs, float* xd,
                          void* ws, size_t ws_bytes, void* stream) {
+    const DiffuseRoute r = diffuse_route(mb, C);
     Bump b(ws, ws_bytes);
-    if (diffuse_ok(mb, C) && time && diffuse_aligned(x, xd, xs, mb->evecs, time, mb->evals)) {      // one launch
-        float* dws = b.f(diffuse_ws_floats(mb));
-        if (!b.ok) return DN_ERR_INVALID;
-        DfLaunch L = diffuse_new(mb, dws);
-        L.x = x; L.time = time; L.xs = xs; L.out = xd;
-        return dn_launch_diffuse(L, S(stream));
-    }
-    float* partial = b.f((size_t)mb->n_chunks * mb->k_eig * C);
-    float* ys = b.f((size_t)mb->n_mesh * mb->k_eig * C);
-    float* wide_ws = bw_ok(mb, C) ? b.f(dn_backproject_wide_ws_floats(mb->n_mesh, mb->k_eig, C)) : nullptr;
+    const DiffuseWs w = diffuse_layout(b, mb, C, r, true, false);
     if (!b.ok) return DN_ERR_INVALID;
-    DN_CHECK(to_basis_partials(mb, x, C, true, partial, S(stream)));
-    DN_CHECK(dn_launch_spec_fwd(partial, mb->mesh_chunk_off, mb->evals, time, xs, ys, mb->n_mesh, mb->k_eig, C, S(stream)));
-    return from_basis(mb, ys, C, xd, nullptr, false, S(stream), F16(), wide_ws);
+    return diffuse_fwd(mb, r, w, x, time, C, xs, xd, S(stream), time != nullptr);
 }
 int dn_diffusion_bwd_f32(const dn_mesh_batch_t* mb, const float* d_xd, const float* xs, const float* time, int C,
                          const float* d_x_add, float* d_x, float* d_time, void* ws, size_t ws_bytes, void* stream) {
+    const DiffuseRoute r = diffuse_route(mb, C);
     Bump b(ws, ws_bytes);
-    if (diffuse_ok(mb, C) && xs && diffuse_aligned(d_xd, d_x, xs, mb->evecs, time, d_x_add)) {      // one launch + the d_t row sum
-        float* dws = b.f(diffuse_ws_floats(mb));
-        float* dtp = b.f((size_t)diffuse_dt_rows(mb) * C);
-        if (!b.ok) return DN_ERR_INVALID;
-        DfLaunch L = diffuse_new(mb, dws);
-        L.bwd = 1; L.x = d_xd; L.time = time; L.xs = const_cast<float*>(xs); L.out = d_x; L.add = d_x_add; L.dt_part = dtp;
-        DN_CHECK(dn_launch_diffuse(L, S(stream)));
-        return dn_launch_reduce(dtp, d_time, diffuse_dt_rows(mb), C, C, S(stream));
-    }
-    float* partial = b.f((size_t)mb->n_chunks * mb->k_eig * C);
-    float* dxs = b.f((size_t)mb->n_mesh * mb->k_eig * C);
-    const int dt_rows = dn_spec_bwd_dt_rows(mb->n_mesh, mb->k_eig);
-    float* dtp = b.f((size_t)dt_rows * C);
+    const DiffuseWs w = diffuse_layout(b, mb, C, r, false, true);
     if (!b.ok) return DN_ERR_INVALID;
-    DN_CHECK(to_basis_partials(mb, d_xd, C, false, partial, S(stream)));
-    if (dn_spec_bwd_fused_ok(partial, time, xs, dxs, dtp, C)) {
-        DN_CHECK(dn_launch_spec_bwd_fused(partial, mb->mesh_chunk_off, mb->evals, time, xs, dxs, dtp, mb->n_mesh, mb->k_eig, C, S(stream), nullptr));
-        DN_CHECK(dn_launch_reduce(dtp, d_time, dt_rows, C, C, S(stream)));
-    } else {
-        DN_CHECK(dn_launch_seg_reduce(partial, mb->mesh_chunk_off, mb->n_mesh, 0, dxs, (long long)mb->k_eig * C, S(stream)));
-        DN_CHECK(dn_launch_spec_bwd(dxs, mb->evals, time, xs, dtp, mb->n_mesh, mb->k_eig, C, S(stream)));
-        DN_CHECK(dn_launch_reduce(dtp, d_time, mb->n_mesh, C, C, S(stream)));
-    }
-    return from_basis(mb, dxs, C, d_x, d_x_add, true, S(stream));   // d_x_add may be NULL
+    return diffuse_bwd(mb, r, w, d_xd, xs, time, C, d_x_add, d_x, d_time, S(stream), xs != nullptr);
 }
 
 // ------------------------------------------------------------------ spectral-gradient operands (dn_spectral.hip)
@@ -498,17 +529,22 @@ int dn_spectral_units(const int32_t* sizes, int n_mesh, int k_eig, dn_tile_t* un
     return dn_sg_units_host(sizes, n_mesh, k_eig, reinterpret_cast<DnTile*>(units));
 }
 size_t dn_spectral_pack_bytes(int n_units, int k_eig) { return dn_sg_pack_elems(n_units, k_eig) * sizeof(uint4); }
-size_t dn_spectral_pack_workspace_bytes(const dn_mesh_batch_t* mb) { return 2 * pad256((size_t)mb->v_total * mb->k_eig) + 512; }
+struct SgPackWs { float *gpx, *gpy; };      // gradX evecs, gradY evecs [V, K]
+static SgPackWs sg_pack_layout(Bump& b, const dn_mesh_batch_t* mb) {
+    return SgPackWs{b.f((size_t)mb->v_total * mb->k_eig), b.f((size_t)mb->v_total * mb->k_eig)};
+}
+size_t dn_spectral_pack_workspace_bytes(const dn_mesh_batch_t* mb) {
+    return ws_query([&](Bump& b) { sg_pack_layout(b, mb); });
+}
 int dn_spectral_pack_f32(const dn_mesh_batch_t* mb, const dn_tile_t* units, int n_units, void* sg_pack, float* sg_amax, void* ws, size_t ws_bytes,
                          void* stream) {
     if (!mb || !units || n_units <= 0 || !sg_pack || !sg_amax || !mb->evecs || !mb->g_rowptr || !mb->g_col || !mb->g_vx || !mb->g_vy ||
         mb->k_eig % 32 != 0 || mb->k_eig > 256 || !al16(mb->evecs) || !al16(sg_pack))
         return DN_ERR_INVALID;
     Bump b(ws, ws_bytes);
-    float* gpx = b.f((size_t)mb->v_total * mb->k_eig);
-    float* gpy = b.f((size_t)mb->v_total * mb->k_eig);
+    const SgPackWs w = sg_pack_layout(b, mb);
     if (!b.ok) return DN_ERR_INVALID;
-    return dn_launch_sg_pack(T(units), n_units, mb->n_mesh, mb->k_eig, mb->evecs, mb->g_rowptr, mb->g_col, mb->g_vx, mb->g_vy, gpx, gpy, sg_amax,
+    return dn_launch_sg_pack(T(units), n_units, mb->n_mesh, mb->k_eig, mb->evecs, mb->g_rowptr, mb->g_col, mb->g_vx, mb->g_vy, w.gpx, w.gpy, sg_amax,
                              reinterpret_cast<uint4*>(sg_pack), S(stream));
 }
 
@@ -522,8 +558,12 @@ int dn_grad_apply_bwd_f32(const dn_mesh_batch_t* mb, const float* d_gx, const fl
 }
 
 // ------------------------------------------------------------------ gradient features
+struct GradfeatWs { float *partial, *ddots, *psum; };
+static GradfeatWs gradfeat_layout(Bump& b, const dn_mesh_batch_t* mb, int C) {
+    return GradfeatWs{b.f((size_t)mb->n_chunks * 4 * C * C), b.f((size_t)mb->v_total * C), b.f((size_t)4 * C * C)};
+}
 size_t dn_gradfeat_workspace_bytes(const dn_mesh_batch_t* mb, int C) {
-    return pad256((size_t)mb->n_chunks * 4 * C * C) + pad256((size_t)mb->v_total * C) + pad256((size_t)4 * C * C) + 512;
+    return ws_query([&](Bump& b) { gradfeat_layout(b, mb, C); });
 }
 int dn_gradfeat_fwd_f32(const dn_mesh_batch_t* mb, const float* gx, const float* gy, const float* A_re, const float* A_im,
                         int C, float* g, float* bre, float* bim, void* stream) {
@@ -533,14 +573,12 @@ int dn_gradfeat_bwd_f32(const dn_mesh_batch_t* mb, const float* d_g, const float
                         const float* bre, const float* bim, const float* A_re, const float* A_im, int C,
                         float* d_gx, float* d_gy, float* dA_re, float* dA_im, void* ws, size_t ws_bytes, void* stream) {
     Bump b(ws, ws_bytes);
-    float* partial = b.f((size_t)mb->n_chunks * 4 * C * C);
-    float* ddots = b.f((size_t)mb->v_total * C);
-    float* psum = b.f((size_t)4 * C * C);
+    const GradfeatWs w = gradfeat_layout(b, mb, C);
     if (!b.ok) return DN_ERR_INVALID;
     // d_dots = d_g * (1 - g^2)   (the fused block folds this into the epilogue of the d_h0 product)
-    DN_CHECK(dn_launch_dtanh(d_g, g, ddots, (long long)mb->v_total * C, S(stream)));
-    DN_CHECK(gradfeat_bwd_weights(mb, ddots, gx, gy, C, dA_re, A_im ? dA_im : nullptr, partial, psum, S(stream)));
-    return gradfeat_bwd_inputs(mb, ddots, gx, gy, bre, bim, A_re, A_im, C, d_gx, d_gy, S(stream));
+    DN_CHECK(dn_launch_dtanh(d_g, g, w.ddots, (long long)mb->v_total * C, S(stream)));
+    DN_CHECK(gradfeat_bwd_weights(mb, w.ddots, gx, gy, C, dA_re, A_im ? dA_im : nullptr, w.partial, w.psum, S(stream)));
+    return gradfeat_bwd_inputs(mb, w.ddots, gx, gy, bre, bim, A_re, A_im, C, d_gx, d_gy, S(stream));
 }
 
 // ------------------------------------------------------------------ nn.Linear
@@ -552,8 +590,12 @@ static size_t linear_partial_elems(const dn_mesh_batch_t* mb, int C_in, int C_ou
     }
     return part;
 }
-size_t dn_linear_workspace_bytes(const dn_mesh_batch_t* mb, int C_in, int C_out) {
-    return pad256(linear_partial_elems(mb, C_in, C_out)) + pad256((size_t)mb->n_chunks * C_out) + 512;
+struct LinearWs { float *partial, *colsum; };
+static LinearWs linear_layout(Bump& b, const dn_mesh_batch_t* mb, int C_in, int C_out) {
+    return LinearWs{b.f(linear_partial_elems(mb, C_in, C_out)), b.f((size_t)mb->n_chunks * C_out)};
+}
+size_t dn_linear_workspace_bytes(const dn_mesh_batch_t* mb, int C_in, int C_out) {      // (the backward's; the forward takes no workspace)
+    return ws_query([&](Bump& b) { linear_layout(b, mb, C_in, C_out); });
 }
 // max |t| of a tensor nobody tracked while producing it: one measuring pass, accumulated into *word
 static int measure_amax(const float* t, long long n, float* word, hipStream_t st) {
@@ -581,8 +623,8 @@ int dn_linear_bwd_f32(const dn_mesh_batch_t* mb, const float* d_out, const float
 int dn_linear_bwd_amax_f32(const dn_mesh_batch_t* mb, const float* d_out, const float* x, const float* W, int C_in, int C_out,
                            float* d_x, float* dW, float* db, float* d_x_amax, void* ws, size_t ws_bytes, void* stream) {
     Bump b(ws, ws_bytes);
-    float* partial = b.f(linear_partial_elems(mb, C_in, C_out));
-    float* colsum = b.f((size_t)mb->n_chunks * C_out);
+    const LinearWs w = linear_layout(b, mb, C_in, C_out);
+    float *partial = w.partial, *colsum = w.colsum;
     if (!b.ok) return DN_ERR_INVALID;
     const float* ins[1] = {x};
     const int ws_[1] = {C_in};
@@ -632,27 +674,69 @@ enum { AW_IN = 0, AW_YS, AW_MISC, AW_WA, AW_W0, AW_D0 = AW_W0 + DN_MAX_MLP_LAYER
 // sets must not overlap: the zeroing workgroup runs concurrently with the storing ones (it once wiped the weight magnitude in 1 call of 2000)
 enum { SW_X = 0, SW_XD, SW_G, SW_H0 };                                                                                          // saved words
 static_assert(SW_H0 + DN_MAX_MLP_LAYERS <= DN_BLOCK_AMAX_WORDS, "saved amax words");
-static bool block_f16_ok(const dn_mesh_batch_t* mb, const dn_block_params_t* p) {
-    if (!opt(O_F16) || (p->flags & DN_BLOCK_NO_F16)) return false;
-    auto ok = [](int w) { return w >= 128 && w % 32 == 0; };
-    if (!ok(p->C) || !ok(mb->k_eig)) return false;
-    for (int j = 1; j < p->n_mlp; ++j) if (!ok(p->widths[j])) return false;
-    return true;
-}
-static size_t amax_ws(void) { return pad256(AW_COUNT + DN_BLOCK_AMAX_WORDS + 2); }
-// The chained row kernels (dn_chain.hip forward, dn_chain_bwd.hip backward) take the block's row work -- gradient gather, gradient features,
-// MiniMLP and their gradients -- when the shapes are the ones they are written for and the magnitude words exist.  Option "chain" = 0
-// keeps the unfused launches (dn_set_option: the tests flip it at run time).
+// ---- BlockRoute: which engines one block call may take, computed ONCE from (mb, p, kind) and the options.  The size queries,
+// dn_block_tracks_amax, the layouts and the bodies all read this one value; the conditions on a call's pointers (alignment, sv->amax,
+// MiniMLP depth of the backward) refine it in the call and are written there as `route.x && ...`.
 // kind: 0 = forward without saved activations (inference), 1 = forward saving activations (training), 2 = backward.
-// Measured on MI355X (tools/kbench, block at C = K = 128, chained / unfused, us; round 5, profiles/r05_chain_hh_sweep.txt -- the chained kernels
-// with one 16-row half per wave where that is faster, see chain_hh below):
-//     vertices        7k        20k       40k       80k       160k
-//     inference     64/86     88/121   122/188   203/299   365/509
-//     training      66/90     99/120   145/194   230/307   447/507
-//     backward     114/139   185/243   290/376   471/574   822/933
-// The chained kernels win at every size in every role since the one-half-per-wave form exists (round 4: the training forward lost between
-// 20k and 80k rows and was only taken from 100k); "chain_min_rows" / "chain_small_rows" (both 0 now) can still carve a window for the
-// unfused training forward: the tests' "mixed" mode uses them.
+struct BlockRoute {
+    bool f16;       // the split-fp16 engine (above) for the unfused products
+    // The chained row kernels (dn_chain.hip forward, dn_chain_bwd.hip backward) take the block's row work -- gradient gather, gradient features,
+    // MiniMLP and their gradients -- when the shapes are the ones they are written for and the magnitude words exist.  Option "chain" = 0
+    // keeps the unfused launches (dn_set_option: the tests flip it at run time).
+    // Measured on MI355X (tools/kbench, block at C = K = 128, chained / unfused, us; round 5, profiles/r05_chain_hh_sweep.txt -- the chained kernels
+    // with one 16-row half per wave where that is faster, see hh below):
+    //     vertices        7k        20k       40k       80k       160k
+    //     inference     64/86     88/121   122/188   203/299   365/509
+    //     training      66/90     99/120   145/194   230/307   447/507
+    //     backward     114/139   185/243   290/376   471/574   822/933
+    // The chained kernels win at every size in every role since the one-half-per-wave form exists (round 4: the training forward lost between
+    // 20k and 80k rows and was only taken from 100k); "chain_min_rows" / "chain_small_rows" (both 0 now) can still carve a window for the
+    // unfused training forward: the tests' "mixed" mode uses them.
+    bool chain;
+    // 16-row halves per wave of the chained kernels: 2 (a weight fragment read feeds two MFMAs) for batches that fill the device, 1 for small ones
+    // (twice the waves, half the serial product chain each): one ~7k-vertex mesh per step is 219 32-row waves on 1024 SIMDs.  Option "chain_hh"
+    // forces either (tests, A/B).
+    // Measured (tools/kbench, block forward / backward, us, HH = 2 -> 1; profiles/r05_chain_hh_sweep.txt): 7k rows 90 -> 66 / 134 -> 114,
+    // 20k 117 -> 99 / 198 -> 185, 40k 168 -> 145 / 319 -> 290, 80k 267 -> 230 / 502 -> 471, 160k 457 -> 447 / 822 -> 833: the forward takes one
+    // half per wave at every size measured, the backward up to ~100k rows.
+    int hh;
+    // The spectral-gradient form of the chained forward (dn_spectral.hip, dn_chain.hip KE > 0): batches that carry the packed operands, shapes the
+    // kernel is instantiated for, one 16-row half per wave (the forward's form up to 262144 rows); not with the one-launch diffusion operator.
+    // Option "spectral_grad": 1 (default) = the inference forward at every size, the training forward up to 65536 rows; 2 = both at every size; 0 = never.
+    // Measured (tools/kbench block_inf / block_fwd, us, spectral / gather form, same box; profiles/r06_sg_sweep.txt):
+    //     vertices      7k          20k         40k         80k         160k        240k       64 x 2k
+    //     inference   58.9/65.3   75.2/82.4   103/117     169/185     323/334     448/476     274/276
+    //     training    60.8/66.7   88.5/92.3   122/132     212/203     389/390     545/581     326/317
+    // The inference forward gains at every size (no back-projection launch, no xd round trip); the training forward also writes xd, gx, gy from the
+    // kernel (13 instead of 10 arrays of [V, C] through it) and is level with back-projection + gather from ~80k rows on (bench.py headline, two
+    // runs each on one box: 30.82 / 30.85 M vertices/s against 31.02 / 31.02).
+    bool sg;
+    DiffuseRoute d;     // one-launch diffusion, direct and wide back-projection
+};
+static BlockRoute block_route(const dn_mesh_batch_t* mb, const dn_block_params_t* p, int kind) {
+    BlockRoute r;
+    r.d = diffuse_route(mb, p->C);
+    auto wide_enough = [](int w) { return w >= 128 && w % 32 == 0; };
+    r.f16 = opt(O_F16) && !(p->flags & DN_BLOCK_NO_F16) && wide_enough(p->C) && wide_enough(mb->k_eig);
+    for (int j = 1; j < p->n_mlp; ++j) r.f16 = r.f16 && wide_enough(p->widths[j]);
+    r.chain = opt(O_CHAIN) && opt(O_F16) && !(p->with_grad && !mb->grad_norm) &&               // "f16" = 0: split-bf16 engine everywhere (A/B runs)
+              !(p->flags & (DN_BLOCK_NO_CHAIN | DN_BLOCK_NO_F16)) &&                             // per-call engine choice (include/diffnet_hip.h)
+              !(kind == 1 && mb->v_total < opt(O_CHAIN_MIN_ROWS) && mb->v_total > opt(O_CHAIN_SMALL_ROWS)) &&
+              dn_chain_eligible(p->C, p->n_mlp, p->widths, p->with_grad, mb->g_nnz, mb->v_total, kind == 2);
+    const int hh = opt(O_CHAIN_HH);
+    if (kind < 2 && p->C >= 256) r.hh = 2;       // (the one form of the C = 256 forward)
+    else if (hh == 1 || hh == 2) r.hh = hh;
+    else r.hh = mb->v_total <= (kind == 2 ? 100000 : 262144) ? 1 : 2;
+    const int o = (p->flags & DN_BLOCK_NO_SPECTRAL_GRAD) ? 0 : ((p->flags & DN_BLOCK_SPECTRAL_GRAD_ALWAYS) ? 2 : opt(O_SPECTRAL_GRAD));
+    // (C = K = 256, the two-launch form: measured SLOWER than back-projection + gather -- BASELINE config 4 at 28.2 M vertices/s against 29.1 M: its
+    // spectral launch reads 0.61 GB of operands and writes 0.61 GB of xd / gx / gy that the chain reads back, 366 us where ~250 would pay -- and
+    // therefore only taken when asked for: option value 2 / DN_BLOCK_SPECTRAL_GRAD_ALWAYS)
+    r.sg = o && kind < 2 && (o >= 2 || (p->C < 256 && (kind == 0 || mb->v_total <= 65536))) && mb->sg_pack && mb->sg_units && mb->sg_amax && mb->sg_n_units > 0 &&
+           al16(mb->sg_pack) && al16(mb->sg_amax) &&
+           mb->sg_n_units <= 100 * dn_num_cus() &&      // (a workgroup's pass table lives in LDS: DN_CH_SG_MAXP = 64 passes of 2 x CUs workgroups)
+           r.chain && dn_chain_sg_eligible(p->C, mb->k_eig, p->with_grad, r.hh) && !r.d.one;
+    return r;
+}
 static bool chain_aligned(const dn_block_params_t* p, const dn_block_saved_t* sv, const float* a, const float* b_, const float* c = nullptr, const float* d = nullptr) {
     bool ok = al16(a) && al16(b_) && al16(c) && al16(d) && al16(p->A_re) && al16(p->A_im) && al16(p->time);
     for (int j = 0; j < p->n_mlp; ++j) ok = ok && al16(p->W[j]) && al16(p->b[j]) && al16(p->mask[j]);
@@ -662,44 +746,6 @@ static bool chain_aligned(const dn_block_params_t* p, const dn_block_saved_t* sv
     }
     return ok;
 }
-// 16-row halves per wave of the chained kernels: 2 (a weight fragment read feeds two MFMAs) for batches that fill the device, 1 for small ones
-// (twice the waves, half the serial product chain each): one ~7k-vertex mesh per step is 219 32-row waves on 1024 SIMDs.  Option "chain_hh"
-// forces either (tests, A/B).
-// Measured (tools/kbench, block forward / backward, us, HH = 2 -> 1; profiles/r05_chain_hh_sweep.txt): 7k rows 90 -> 66 / 134 -> 114,
-// 20k 117 -> 99 / 198 -> 185, 40k 168 -> 145 / 319 -> 290, 80k 267 -> 230 / 502 -> 471, 160k 457 -> 447 / 822 -> 833: the forward takes one
-// half per wave at every size measured, the backward up to ~100k rows.
-static int chain_hh(const dn_mesh_batch_t* mb, bool backward = false, int C = 128) {
-    if (C >= 256) return 2;       // (the one form of the C = 256 forward)
-    const int f = opt(O_CHAIN_HH);
-    if (f == 1 || f == 2) return f;
-    return mb->v_total <= (backward ? 100000 : 262144) ? 1 : 2;
-}
-static bool block_chain_ok(const dn_mesh_batch_t* mb, const dn_block_params_t* p, int kind) {
-    if (!opt(O_CHAIN) || !opt(O_F16) || (p->with_grad && !mb->grad_norm)) return false;      // "f16" = 0: split-bf16 engine everywhere (A/B runs)
-    if (p->flags & (DN_BLOCK_NO_CHAIN | DN_BLOCK_NO_F16)) return false;                        // per-call engine choice (include/diffnet_hip.h)
-    if (kind == 1 && mb->v_total < opt(O_CHAIN_MIN_ROWS) && mb->v_total > opt(O_CHAIN_SMALL_ROWS)) return false;
-    return dn_chain_eligible(p->C, p->n_mlp, p->widths, p->with_grad, mb->g_nnz, mb->v_total, kind == 2);
-}
-// The spectral-gradient form of the chained forward (dn_spectral.hip, dn_chain.hip KE > 0): batches that carry the packed operands, shapes the
-// kernel is instantiated for, one 16-row half per wave (the forward's form up to 262144 rows); not with the one-launch diffusion operator.
-// Option "spectral_grad": 1 (default) = the inference forward at every size, the training forward up to 65536 rows; 2 = both at every size; 0 = never.
-// Measured (tools/kbench block_inf / block_fwd, us, spectral / gather form, same box; profiles/r06_sg_sweep.txt):
-//     vertices      7k          20k         40k         80k         160k        240k       64 x 2k
-//     inference   58.9/65.3   75.2/82.4   103/117     169/185     323/334     448/476     274/276
-//     training    60.8/66.7   88.5/92.3   122/132     212/203     389/390     545/581     326/317
-// The inference forward gains at every size (no back-projection launch, no xd round trip); the training forward also writes xd, gx, gy from the
-// kernel (13 instead of 10 arrays of [V, C] through it) and is level with back-projection + gather from ~80k rows on (bench.py headline, two
-// runs each on one box: 30.82 / 30.85 M vertices/s against 31.02 / 31.02).
-static bool block_sg_ok(const dn_mesh_batch_t* mb, const dn_block_params_t* p, int kind) {
-    const int o = (p->flags & DN_BLOCK_NO_SPECTRAL_GRAD) ? 0 : ((p->flags & DN_BLOCK_SPECTRAL_GRAD_ALWAYS) ? 2 : opt(O_SPECTRAL_GRAD));
-    // (C = K = 256, the two-launch form: measured SLOWER than back-projection + gather -- BASELINE config 4 at 28.2 M vertices/s against 29.1 M: its
-    // spectral launch reads 0.61 GB of operands and writes 0.61 GB of xd / gx / gy that the chain reads back, 366 us where ~250 would pay -- and
-    // therefore only taken when asked for: option value 2 / DN_BLOCK_SPECTRAL_GRAD_ALWAYS)
-    return o && kind < 2 && (o >= 2 || (p->C < 256 && (kind == 0 || mb->v_total <= 65536))) && mb->sg_pack && mb->sg_units && mb->sg_amax && mb->sg_n_units > 0 && al16(mb->sg_pack) && al16(mb->sg_amax) &&
-           mb->sg_n_units <= 100 * dn_num_cus() &&      // (a workgroup's pass table lives in LDS: DN_CH_SG_MAXP = 64 passes of 2 x CUs workgroups)
-           block_chain_ok(mb, p, kind) && dn_chain_sg_eligible(p->C, mb->k_eig, p->with_grad, chain_hh(mb, false, p->C)) && !diffuse_ok(mb, p->C);
-}
-static size_t sg_piece_floats(const dn_mesh_batch_t* mb, int C) { return (size_t)mb->n_mesh * (mb->k_eig / 32) * (2 * (C / 16) * 64) * 4; }
 // Product classes of the block; option "f16_mask" (diagnostic) selects which of them run on the split-fp16 engine.
 // Default: the row products (gradient features, MLP, input gradients, backward back-projection).  Not the split-V projections
 // evecs^T x (their lock-step kernel gains nothing: 55 -> 54.6 us, and leaving them out spares the transposed gather a magnitude
@@ -713,152 +759,161 @@ static F16 f16_if(int bit, const F16& f) { if (f16_mask() & bit) return f; F16 r
 
 int dn_block_tracks_amax(const dn_mesh_batch_t* mb, const dn_block_params_t* p, int call) {
     if (!mb || !block_params_ok(p) || call < 0 || call > 2) return 0;
-    if (block_f16_ok(mb, p)) return 1;
-    return (call < 2 && block_chain_ok(mb, p, call)) ? 1 : 0;      // (the chained backward alone does not produce max |d_x|)
+    const BlockRoute r = block_route(mb, p, call);
+    return (r.f16 || (call < 2 && r.chain)) ? 1 : 0;      // (the chained backward alone does not produce max |d_x|)
+}
+
+// The weight pieces of the chained kernels.  Their ORDER is the kernels' contract -- forward: column blocks (gradient-feature pieces, which the
+// kernel streams once per 16-row half of a wave, then layer 0 with the g segment first (columns 2C..), then x, xd, then the other layers);
+// backward: transposed, last layer first, the gradient-feature pieces last and repeated once per 16-row half.
+static void chain_piece(ChainPrepArgs& pa, int& np, const float* Wm, const float* Wm2, float* word, int ld, int col0, int transposed = 0, int row0 = 0) {
+    ChainPrepPiece& q = pa.pc[np++]; q.W = Wm; q.W2 = Wm2; q.amax = word; q.ld = ld; q.col0 = col0; q.transposed = transposed; q.row0 = row0;
+}
+static int chain_pieces_fwd(ChainPrepArgs& pa, const dn_block_params_t* p, float* aw, int* n_gf) {
+    const int C = p->C, NK = C / 32;
+    int np = 0;
+    if (p->with_grad)
+        for (int T = 0; T < NK; ++T) {
+            chain_piece(pa, np, p->A_re, p->with_rot ? p->A_im : nullptr, aw + AW_WA, C, 32 * T);
+            if (p->with_rot) chain_piece(pa, np, p->A_im, p->A_re, aw + AW_WA, C, 32 * T);
+        }
+    *n_gf = np;
+    for (int sg = 0; sg < (p->with_grad ? 3 : 2); ++sg) {
+        const int seg = p->with_grad ? (sg + 2) % 3 : sg;
+        for (int T = 0; T < NK; ++T) chain_piece(pa, np, p->W[0], nullptr, aw + AW_W0, p->widths[0], seg * C + 32 * T);
+    }
+    for (int j = 1; j < p->n_mlp; ++j)
+        for (int T = 0; T < NK; ++T) chain_piece(pa, np, p->W[j], nullptr, aw + AW_W0 + j, C, 32 * T);
+    return np;
+}
+static int chain_pieces_bwd(ChainPrepArgs& pa, const dn_block_params_t* p, float* aw, int hh) {
+    const int C = p->C, NK = C / 32;
+    int np = 0;
+    auto piece = [&](const float* Wm, const float* Wm2, float* word, int ld, int row0, int T) { chain_piece(pa, np, Wm, Wm2, word, ld, 32 * T, 1, row0); };
+    for (int j = p->n_mlp - 1; j >= 1; --j)
+        for (int T = 0; T < NK; ++T) piece(p->W[j], nullptr, aw + AW_W0 + j, C, 0, T);
+    for (int sg = 0; sg < (p->with_grad ? 3 : 2); ++sg)
+        for (int T = 0; T < NK; ++T) piece(p->W[0], nullptr, aw + AW_W0, p->widths[0], sg * C, T);
+    if (p->with_grad)
+        for (int rep = 0; rep < hh; ++rep)
+            for (int T = 0; T < NK; ++T) {
+                piece(p->A_re, p->with_rot ? p->A_im : nullptr, aw + AW_WA, C, 0, T);
+                if (p->with_rot) piece(p->A_im, p->A_re, aw + AW_WA, C, 0, T);
+            }
+    return np;
+}
+
+// ---- magnitude words of a block call: ONE launch stores the weight magnitudes and does the call's bookkeeping (CallPrep: the words its kernels
+// accumulate into zeroed, ...) -- the weight-preparation kernel of a chained call, else amax_init -- then one measuring pass for what the caller did not pass
+struct BlockWords {     // what differs between the forward's and the backward's
+    const float *in, *given; float* in_word;      // the call's input [V, C]; the caller's word for it, or null: measured into in_word
+    float* keep;                                   // forward saving activations: the saved set's copy of that word (the backward multiplies by x again)
+    float* zero[2]; int zero_n[2];                 // the call's words outside its workspace that its kernels accumulate into
+    bool mass, clamp;                              // the split-fp16 projection scales by max |mass|; clamp p->time (layers.py:48-49) in this launch
+    float* chain_ws; int bwd_hh;                   // chained call: where its weight pieces go; 0 = the forward's piece list, else the backward's for that wave shape
+};
+struct WordsFound { const float *in_amax, *ev_amax, *ms_amax; int np, n_gf; };      // words of the input, evecs, mass; chained: pieces written, the forward's gradient-feature ones
+static int block_words(const dn_mesh_batch_t* mb, const dn_block_params_t* p, float* aw, bool f16, const BlockWords& w, hipStream_t st, WordsFound& c) {
+    const int C = p->C;
+    float* spare = aw + AW_COUNT + DN_BLOCK_AMAX_WORDS;      // two words behind the call's and the inference forward's saved set: evecs, mass
+    CallPrep prep; memset(&prep, 0, sizeof(prep));
+    prep.zero_range(aw, AW_WA);                                                  // AW_IN, AW_YS, AW_MISC
+    prep.zero_range(aw + AW_D0, DN_MAX_MLP_LAYERS + 1 + DN_BLOCK_AMAX_WORDS + 2);
+    for (int i = 0; i < 2; ++i) prep.zero_range(w.zero[i], w.zero_n[i]);
+    c.in_amax = w.given; c.ev_amax = mb->evecs_amax; c.ms_amax = mb->mass_amax;
+    const bool measure = !w.given || (f16 && (!c.ev_amax || (w.mass && !c.ms_amax)));
+    if (w.given && w.keep && !measure) { prep.copy_src = w.given; prep.copy_dst = w.keep; }
+    if (w.clamp) { prep.clamp_p = const_cast<float*>(p->time); prep.clamp_n = C; prep.clamp_min = DN_MIN_TIME; }
+    if (w.chain_ws) {
+        ChainPrepArgs pa; memset(&pa, 0, sizeof(pa));
+        c.np = w.bwd_hh ? chain_pieces_bwd(pa, p, aw, w.bwd_hh) : chain_pieces_fwd(pa, p, aw, &c.n_gf);
+        pa.out = reinterpret_cast<uint4*>(w.chain_ws); pa.prep = prep;
+        DN_CHECK(dn_launch_chain_prep(pa, c.np, C, st));
+    } else {
+        AmaxInit in; memset(&in, 0, sizeof(in));
+        if (p->with_grad) { in.jobs.push(p->A_re, (long long)C * C, aw + AW_WA); if (p->with_rot) in.jobs.push(p->A_im, (long long)C * C, aw + AW_WA); }
+        for (int j = 0; j < p->n_mlp && in.jobs.count < DN_AMAX_MAX_JOBS; ++j) in.jobs.push(p->W[j], (long long)p->widths[j] * p->widths[j + 1], aw + AW_W0 + j);
+        in.prep = prep;
+        DN_CHECK(dn_launch_amax_init(in, st));
+    }
+    if (!measure) return 0;
+    AmaxJobs jobs; jobs.count = 0;
+    if (!w.given) { jobs.push(w.in, (long long)mb->v_total * C, w.in_word); c.in_amax = w.in_word; }
+    if (f16 && !c.ev_amax) { jobs.push(mb->evecs, (long long)mb->v_total * mb->k_eig, spare); c.ev_amax = spare; }
+    if (f16 && w.mass && !c.ms_amax) { jobs.push(mb->mass, (long long)mb->v_total, spare + 1); c.ms_amax = spare + 1; }
+    DN_CHECK(dn_launch_amax(jobs, st));
+    if (w.given && w.keep) DN_CHECK((int)hipMemcpyAsync(w.keep, w.given, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// ---- forward
+struct BlockFwdWs {
+    DiffuseWs d;
+    float *aw, *chain;      // the call's magnitude words; route.chain: the chained kernel's weight pieces
+    float *ysp, *ysa;       // route.sg: the scaled spectrum as weight pieces + its per-mesh magnitudes
+    float *xs, *xd, *gx, *gy, *gf, *h[2];      // inference: what a training call writes to its saved set (the call points these there), and the hidden ping-pong
+    float *bre, *bim;                          // (training only: never regions)
+};
+static BlockFwdWs block_fwd_layout(Bump& b, const dn_mesh_batch_t* mb, const dn_block_params_t* p, const BlockRoute& r, bool with_saved) {
+    const int C = p->C;
+    const size_t VC = (size_t)mb->v_total * C;
+    BlockFwdWs w; memset(&w, 0, sizeof(w));
+    w.d = diffuse_layout(b, mb, C, r.d, true, false);
+    w.aw = b.f(AW_COUNT + DN_BLOCK_AMAX_WORDS + 2);
+    if (r.chain) w.chain = b.f(dn_chain_ws_bytes(C, p->with_grad, p->with_rot, p->n_mlp) / sizeof(float));
+    if (r.sg) { w.ysp = b.f((size_t)mb->n_mesh * (mb->k_eig / 32) * (2 * (C / 16) * 64) * 4); w.ysa = b.f((size_t)2 * mb->n_mesh); }
+    if (!with_saved) {
+        w.xs = b.f((size_t)mb->n_mesh * mb->k_eig * C); w.xd = b.f(VC); w.gx = b.f(VC); w.gy = b.f(VC); w.gf = b.f(VC);
+        for (int i = 0; i < 2; ++i) w.h[i] = b.f((size_t)mb->v_total * max_width(p));
+    }
+    return w;
 }
 size_t dn_block_fwd_workspace_bytes(const dn_mesh_batch_t* mb, const dn_block_params_t* p, int with_saved) {
     if (!block_params_ok(p)) return 0;
-    const size_t VC = (size_t)mb->v_total * p->C;
-    size_t n = pad256((size_t)mb->n_chunks * mb->k_eig * p->C) + pad256((size_t)mb->n_mesh * mb->k_eig * p->C) + amax_ws() + 512;
-    if (block_chain_ok(mb, p, with_saved ? 1 : 0)) n += pad256(dn_chain_ws_bytes(p->C, p->with_grad, p->with_rot, p->n_mlp) / sizeof(float));
-    if (block_sg_ok(mb, p, with_saved ? 1 : 0)) n += pad256(sg_piece_floats(mb, p->C)) + pad256((size_t)2 * mb->n_mesh);
-    if (diffuse_ok(mb, p->C)) n += pad256(diffuse_ws_floats(mb));
-    if (bw_ok(mb, p->C)) n += pad256(dn_backproject_wide_ws_floats(mb->n_mesh, mb->k_eig, p->C));
-    if (!with_saved) {
-        n += pad256((size_t)mb->n_mesh * mb->k_eig * p->C) + 4 * pad256(VC);          // xs, xd, gx, gy, g
-        n += 2 * pad256((size_t)mb->v_total * max_width(p));                            // hidden ping-pong
-    }
-    return n;
+    return ws_query([&](Bump& b) { block_fwd_layout(b, mb, p, block_route(mb, p, with_saved ? 1 : 0), with_saved != 0); });
 }
 int dn_block_fwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, const float* x, float* out,
                      const dn_block_saved_t* sv, void* ws, size_t ws_bytes, void* stream) {
     if (!block_params_ok(p)) return DN_ERR_INVALID;
     hipStream_t st = S(stream);
-    const int C = p->C, K = mb->k_eig;
-    const size_t VC = (size_t)mb->v_total * C;
+    const int C = p->C;
+    const BlockRoute r = block_route(mb, p, sv ? 1 : 0);
     Bump b(ws, ws_bytes);
-    float* partial = b.f((size_t)mb->n_chunks * K * C);
-    float* ys = b.f((size_t)mb->n_mesh * K * C);
-    float* aw = b.f(AW_COUNT + DN_BLOCK_AMAX_WORDS + 2);
-    const bool chain = block_chain_ok(mb, p, sv ? 1 : 0) && (!sv || sv->amax) && chain_aligned(p, sv, x, out);
-    float* chain_ws = block_chain_ok(mb, p, sv ? 1 : 0) ? b.f(dn_chain_ws_bytes(p->C, p->with_grad, p->with_rot, p->n_mlp) / sizeof(float)) : nullptr;
-    const bool sg_ws = block_sg_ok(mb, p, sv ? 1 : 0);
-    float* ysp = sg_ws ? b.f(sg_piece_floats(mb, C)) : nullptr;          // the scaled spectrum as weight pieces + its per-mesh magnitudes
-    float* ysa = sg_ws ? b.f((size_t)2 * mb->n_mesh) : nullptr;
-    const bool sg = chain && sg_ws;                                       // xd, gx, gy computed inside the chained kernel (dn_spectral.hip)
-    float* diffuse_ws = diffuse_ok(mb, C) ? b.f(diffuse_ws_floats(mb)) : nullptr;
-    float* wide_ws = bw_ok(mb, C) ? b.f(dn_backproject_wide_ws_floats(mb->n_mesh, K, C)) : nullptr;   // the spectrum split into ring pieces (K = C = 256)
-    float *xs, *xd, *gx = nullptr, *gy = nullptr, *gf = nullptr, *bre = nullptr, *bim = nullptr;
-    float* hbuf[2] = {nullptr, nullptr};
-    if (sv) {
-        xs = sv->xs; xd = sv->xd; gx = sv->gx; gy = sv->gy; gf = sv->g; bre = sv->bre; bim = sv->bim;
-    } else {
-        xs = b.f((size_t)mb->n_mesh * K * C); xd = b.f(VC);
-        gx = b.f(VC); gy = b.f(VC); gf = b.f(VC);
-        hbuf[0] = b.f((size_t)mb->v_total * max_width(p));
-        hbuf[1] = b.f((size_t)mb->v_total * max_width(p));
-    }
+    BlockFwdWs w = block_fwd_layout(b, mb, p, r, sv != nullptr);
     if (!b.ok) return DN_ERR_INVALID;
-
-    // ---- operand magnitudes for the split-fp16 engine
-    const bool f16 = block_f16_ok(mb, p) && (!sv || sv->amax);          // split-fp16 engine for the unfused products
-    const bool words = f16 || chain;                                      // magnitude words are tracked by this call
-    float* sw = sv ? sv->amax : aw + AW_COUNT;                 // magnitudes of the saved activations (kept for the backward)
-    const float *x_amax = nullptr, *ev_amax = nullptr, *ms_amax = nullptr;
-    ChainPrepArgs pa; memset(&pa, 0, sizeof(pa));
-    int chain_np = 0, chain_ngf = 0;
-    const bool use_chain = chain;
-    if (!words && p->clamp_time) {           // no bookkeeping launch on this path: the clamp is the launch
+    if (sv) { w.xs = sv->xs; w.xd = sv->xd; w.gx = sv->gx; w.gy = sv->gy; w.gf = sv->g; w.bre = sv->bre; w.bim = sv->bim; }
+    // the route refined by this call's pointers; sg: xd, gx, gy computed inside the chained kernel (dn_spectral.hip)
+    const bool chain = r.chain && (!sv || sv->amax) && chain_aligned(p, sv, x, out), sg = chain && r.sg, f16 = r.f16 && (!sv || sv->amax);
+    float *aw = w.aw, *sw = sv ? sv->amax : aw + AW_COUNT;      // call-local words; magnitudes of the saved activations (kept for the backward)
+    WordsFound m; memset(&m, 0, sizeof(m));
+    // ---- magnitude words (tracked by this call if either engine needs them)
+    if (f16 || chain) {
+        const BlockWords bw = {x, p->x_amax, sv ? sw + SW_X : aw + AW_IN, sv ? sw + SW_X : nullptr, {sv ? sw : nullptr, p->out_amax}, {DN_BLOCK_AMAX_WORDS, 1},
+                               true, p->clamp_time != 0, chain ? w.chain : nullptr, 0};
+        DN_CHECK(block_words(mb, p, aw, f16, bw, st, m));
+    } else if (p->clamp_time) {      // no bookkeeping launch on this path: the clamp is the launch
         AmaxInit in; memset(&in, 0, sizeof(in));
-        in.clamp_p = const_cast<float*>(p->time); in.clamp_n = C; in.clamp_min = DN_MIN_TIME;
+        in.prep.clamp_p = const_cast<float*>(p->time); in.prep.clamp_n = C; in.prep.clamp_min = DN_MIN_TIME;
         DN_CHECK(dn_launch_amax_init(in, st));
     }
-    if (words) {
-        // one launch: weight magnitudes (stored), the words the kernels below accumulate into zeroed, the input's word forwarded to the
-        // saved set (the backward multiplies by x again).  With the chained row kernel that launch is its weight-preparation kernel.
-        AmaxInit in; memset(&in, 0, sizeof(in));
-        if (!use_chain) {
-            if (p->with_grad) { in.jobs.push(p->A_re, (long long)C * C, aw + AW_WA); if (p->with_rot) in.jobs.push(p->A_im, (long long)C * C, aw + AW_WA); }
-            for (int j = 0; j < p->n_mlp && in.jobs.count < DN_AMAX_MAX_JOBS; ++j) in.jobs.push(p->W[j], (long long)p->widths[j] * p->widths[j + 1], aw + AW_W0 + j);
-        }
-        in.zero_range(aw, AW_WA);                                                  // AW_IN, AW_YS, AW_MISC
-        in.zero_range(aw + AW_D0, DN_MAX_MLP_LAYERS + 1 + DN_BLOCK_AMAX_WORDS + 2);
-        if (sv) in.zero_range(sw, DN_BLOCK_AMAX_WORDS);
-        in.zero_range(p->out_amax, 1);
-        x_amax = p->x_amax;
-        ev_amax = mb->evecs_amax; ms_amax = mb->mass_amax;
-        const bool measure = !x_amax || (f16 && (!ev_amax || !ms_amax));
-        if (x_amax && sv && !measure) { in.copy_src = x_amax; in.copy_dst = sw + SW_X; }
-        if (p->clamp_time) { in.clamp_p = const_cast<float*>(p->time); in.clamp_n = C; in.clamp_min = DN_MIN_TIME; }     // layers.py:48-49, in this launch
-        if (use_chain) {
-            const int NK = C / 32;
-            auto piece = [&](const float* Wm, const float* Wm2, float* word, int ld, int col0) {
-                ChainPrepPiece& q = pa.pc[chain_np++]; q.W = Wm; q.W2 = Wm2; q.amax = word; q.ld = ld; q.col0 = col0; };
-            if (p->with_grad)
-                for (int T = 0; T < NK; ++T) {      // (streamed once per 16-row half of a wave by the kernel)
-                    piece(p->A_re, p->with_rot ? p->A_im : nullptr, aw + AW_WA, C, 32 * T);
-                    if (p->with_rot) piece(p->A_im, p->A_re, aw + AW_WA, C, 32 * T);
-                }
-            chain_ngf = chain_np;
-            for (int sg = 0; sg < (p->with_grad ? 3 : 2); ++sg) {      // layer 0: the g segment first (columns 2C..), then x, xd
-                const int seg = p->with_grad ? (sg + 2) % 3 : sg;
-                for (int T = 0; T < NK; ++T) piece(p->W[0], nullptr, aw + AW_W0, p->widths[0], seg * C + 32 * T);
-            }
-            for (int j = 1; j < p->n_mlp; ++j)
-                for (int T = 0; T < NK; ++T) piece(p->W[j], nullptr, aw + AW_W0 + j, C, 32 * T);
-            pa.out = reinterpret_cast<uint4*>(chain_ws);
-            for (int r = 0; r < in.nzero; ++r) pa.zero_range(in.zero[r], in.zero_n[r]);
-            pa.copy_src = in.copy_src; pa.copy_dst = in.copy_dst;
-            pa.clamp_p = in.clamp_p; pa.clamp_n = in.clamp_n; pa.clamp_min = in.clamp_min;
-            DN_CHECK(dn_launch_chain_prep(pa, chain_np, C, st));
-        } else {
-            DN_CHECK(dn_launch_amax_init(in, st));
-        }
-        if (measure) {   // a caller without magnitudes (plain C users, the first block of a net): one extra pass over what is missing
-            AmaxJobs jobs; jobs.count = 0;
-            float* fx = sv ? sw + SW_X : aw + AW_IN;
-            if (!x_amax) { jobs.push(x, (long long)VC, fx); x_amax = fx; }
-            if (f16 && !ev_amax) { jobs.push(mb->evecs, (long long)mb->v_total * K, aw + AW_COUNT + DN_BLOCK_AMAX_WORDS); ev_amax = aw + AW_COUNT + DN_BLOCK_AMAX_WORDS; }
-            if (f16 && !ms_amax) { jobs.push(mb->mass, (long long)mb->v_total, aw + AW_COUNT + DN_BLOCK_AMAX_WORDS + 1); ms_amax = aw + AW_COUNT + DN_BLOCK_AMAX_WORDS + 1; }
-            DN_CHECK(dn_launch_amax(jobs, st));
-            if (p->x_amax && sv) DN_CHECK((int)hipMemcpyAsync(sw + SW_X, p->x_amax, sizeof(float), hipMemcpyDeviceToDevice, st));
-        }
-    }
-    auto W = [&](int j) { return (const float*)(aw + AW_W0 + j); };
-
-    // diffusion (layers.py:210): one persistent launch (dn_diffuse.hip) when the batch carries its plan -- both products on the 3-term
-    // engine, as the three-launch form runs them by default -- else projection, spectral step, back-projection
-    if (diffuse_ws && !(f16 && (f16_mask() & (F16_TOB | F16_FROMB))) && diffuse_aligned(x, xd, xs, mb->evecs, p->time, mb->evals)) {
-        DfLaunch L = diffuse_new(mb, diffuse_ws);
-        L.x = x; L.time = p->time; L.xs = xs; L.out = xd;
-        L.out_amax = words ? sw + SW_XD : nullptr;                           // (the chained kernel scales xd by its magnitude)
-        DN_CHECK(dn_launch_diffuse(L, st));
-    } else {
-        {
-            F16 f;
-            if (f16) { f = f16_of(ev_amax, x_amax); f.b.mul = ms_amax; }
-            DN_CHECK(to_basis_partials(mb, x, C, true, partial, st, f16_if(F16_TOB, f)));
-        }
-        DN_CHECK(dn_launch_spec_fwd(partial, mb->mesh_chunk_off, mb->evals, p->time, xs, ys, mb->n_mesh, K, C, st,
-                                    (f16 && (f16_mask() & F16_FROMB)) ? aw + AW_YS : nullptr));   // only the split-fp16 back-projection needs max |ys|
-        if (sg) {
-            // no back-projection launch: the chained kernel multiplies [evecs | gradX evecs | gradY evecs] by the spectrum itself
-            DN_CHECK(dn_launch_spec_pieces(ys, mb->n_mesh, K, C, reinterpret_cast<uint4*>(ysp), ysa, st));
-        } else {
-            F16 fb;
-            if (f16) fb = f16_if(F16_FROMB, f16_of(ev_amax, aw + AW_YS, sw + SW_XD));
-            else if (words) fb.o = sw + SW_XD;                                  // (the chained kernel scales xd by its magnitude)
-            DN_CHECK(from_basis(mb, ys, C, xd, nullptr, false, st, fb, wide_ws));
-        }
-    }
-    if (use_chain) {   // gather -> gradient features -> MiniMLP + residual in one launch (layers.py:213-239)
+    // ---- diffusion (layers.py:210)
+    F16 tob, fromb;
+    if (f16) {
+        tob = f16_of(m.ev_amax, m.in_amax); tob.b.mul = m.ms_amax; tob = f16_if(F16_TOB, tob);
+        fromb = f16_if(F16_FROMB, f16_of(m.ev_amax, aw + AW_YS, sw + SW_XD));
+    } else if (chain) fromb.o = sw + SW_XD;                         // (the chained kernel scales xd by its magnitude)
+    DN_CHECK(diffuse_fwd(mb, r.d, w.d, x, p->time, C, w.xs, w.xd, st, !(f16 && (f16_mask() & (F16_TOB | F16_FROMB))), tob, fromb,
+                         (f16 && (f16_mask() & F16_FROMB)) ? aw + AW_YS : nullptr,      // only the split-fp16 back-projection needs max |ys|
+                         sg ? w.ysp : nullptr, sg ? w.ysa : nullptr));
+    // ---- row work, chained: gather -> gradient features -> MiniMLP + residual in one launch (layers.py:213-239)
+    auto chain_rows = [&]() -> int {
         ChainArgs ca; memset(&ca, 0, sizeof(ca));
         ca.rowptr = mb->g_rowptr; ca.col = mb->g_col; ca.vx = mb->g_vx; ca.vy = mb->g_vy;
-        ca.x = x; ca.xd = xd; ca.V = mb->v_total;
+        ca.x = x; ca.xd = w.xd; ca.V = mb->v_total;
         ca.with_grad = p->with_grad; ca.with_rot = p->with_rot; ca.n_mlp = p->n_mlp;
-        ca.wp = reinterpret_cast<const uint4*>(chain_ws);
+        ca.wp = reinterpret_cast<const uint4*>(w.chain);
         // pieces the kernel streams once per 16-row half: the gradient-feature ones, and at C = 256 layer 0's g segment behind them (dn_chain.hip, G0)
-        ca.n_gf = chain_ngf + ((C >= 256 && p->with_grad) ? C / 32 : 0);
+        ca.n_gf = m.n_gf + ((C >= 256 && p->with_grad) ? C / 32 : 0);
         ca.wa_amax = aw + AW_WA;
         for (int j = 0; j < p->n_mlp; ++j) {
             ca.w_amax[j] = aw + AW_W0 + j; ca.bias[j] = p->b[j];
@@ -870,272 +925,206 @@ int dn_block_fwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, cons
             }
         }
         ca.seed_dev = (const unsigned long long*)p->drop_seed_dev;
-        if (p->with_grad && sv) { ca.gx = gx; ca.gy = gy; ca.g = gf; ca.bre = bre; ca.bim = bim; }
-        if (sg && C >= 256) { ca.gx = gx; ca.gy = gy; }      // (the C = 256 spectral form hands gx, gy from its spectral phase to its gradient-feature stage through memory)
+        if (p->with_grad && sv) { ca.gx = w.gx; ca.gy = w.gy; ca.g = w.gf; ca.bre = w.bre; ca.bim = w.bim; }
+        if (sg && C >= 256) { ca.gx = w.gx; ca.gy = w.gy; }      // (the C = 256 spectral form hands gx, gy from its spectral phase to its gradient-feature stage through memory)
         // (Measured and rejected: gathering gx, gy with the stand-alone CSR kernel first and letting the training chain read them -- the chained
         // kernel drops from 357 to 293 us, but the 87 us gather launch more than eats it: block forward 480 vs 465 us, profiles/r04_pregather.txt.)
         ca.out = out;
-        ca.x_amax = x_amax; ca.xd_amax = sw + SW_XD; ca.grad_norm = mb->grad_norm;
+        ca.x_amax = m.in_amax; ca.xd_amax = sw + SW_XD; ca.grad_norm = mb->grad_norm;
         ca.g_amax = sw + SW_G; ca.out_amax = p->out_amax;
         if (sg) {
             // (C = 256: the kernel writes xd to the buffer and reads it back in layer 0; C <= 128: xd stays in registers, written only when saved)
-            ca.xd = C >= 256 ? xd : nullptr;
+            ca.xd = C >= 256 ? w.xd : nullptr;
             ca.sg_pack = reinterpret_cast<const uint4*>(mb->sg_pack); ca.sg_units = T(mb->sg_units); ca.sg_n_units = mb->sg_n_units; ca.sg_amax = mb->sg_amax;
-            ca.sg_unit_rows = dn_sg_unit_rows(K); ca.sg_n_mesh = mb->n_mesh;
-            ca.ysp = reinterpret_cast<const uint4*>(ysp); ca.ys_amax = ysa;
-            ca.xd_out = (sv || C >= 256) ? xd : nullptr; ca.xd_amax_out = sw + SW_XD;
+            ca.sg_unit_rows = dn_sg_unit_rows(mb->k_eig); ca.sg_n_mesh = mb->n_mesh;
+            ca.ysp = reinterpret_cast<const uint4*>(w.ysp); ca.ys_amax = w.ysa;
+            ca.xd_out = (sv || C >= 256) ? w.xd : nullptr; ca.xd_amax_out = sw + SW_XD;
         }
-        return dn_launch_chain_fwd(chain_np, ca, C, st, chain_hh(mb, false, C));
-    }
-    // gradient features (layers.py:213-226)
-    if (p->with_grad) {
-        DN_CHECK(grad_apply_fwd(mb, xd, C, gx, gy, st, f16 ? sw + SW_G : nullptr, f16 ? sw + SW_XD : nullptr));
-        DN_CHECK(gradfeat_fwd(mb, gx, gy, p->A_re, p->with_rot ? p->A_im : nullptr, C, gf, bre, bim, st,
-                              f16 ? f16_if(F16_GF, f16_of(sw + SW_G, aw + AW_WA)) : F16()));
-    }
-    // MiniMLP on [x | xd | g] + residual (layers.py:229-239)
-    const float* in_ptr[3] = {x, xd, gf};
-    int in_w[3] = {C, C, C};
-    int nseg = p->with_grad ? 3 : 2;
-    for (int j = 0; j < p->n_mlp; ++j) {
-        const bool last = (j == p->n_mlp - 1);
-        float* dst = last ? out : (sv ? sv->h[j] : hbuf[j & 1]);
-        F16 f;
-        if (f16) {
-            f = f16_of(j == 0 ? x_amax : sw + SW_H0 + j - 1, W(j), last ? p->out_amax : sw + SW_H0 + j);
-            if (j == 0) { f.a.p[1] = sw + SW_XD; f.a.c = p->with_grad ? 1.f : 0.f; }      // [x | xd | g], |g| = |tanh| <= 1
+        return dn_launch_chain_fwd(m.np, ca, C, st, r.hh);
+    };
+    // ---- row work, unfused
+    auto unfused_rows = [&]() -> int {
+        // gradient features (layers.py:213-226)
+        if (p->with_grad) {
+            DN_CHECK(grad_apply_fwd(mb, w.xd, C, w.gx, w.gy, st, f16 ? sw + SW_G : nullptr, f16 ? sw + SW_XD : nullptr));
+            DN_CHECK(gradfeat_fwd(mb, w.gx, w.gy, p->A_re, p->with_rot ? p->A_im : nullptr, C, w.gf, w.bre, w.bim, st,
+                                  f16 ? f16_if(F16_GF, f16_of(sw + SW_G, aw + AW_WA)) : F16()));
         }
-        DN_CHECK(linear_fwd(mb, in_ptr, in_w, nseg, p->W[j], p->widths[j], p->b[j], p->widths[j + 1],
-                            last ? DN_EPI_BIAS_RESID : DN_EPI_BIAS_RELU, last ? nullptr : p->mask[j + 1],
-                            last ? x : nullptr, dst, st, last ? 0ull : layer_seed(p->drop_seed, j + 1), (const unsigned long long*)p->drop_seed_dev,
-                            f16_if(F16_MLP, f)));
-        in_ptr[0] = dst; in_w[0] = p->widths[j + 1]; nseg = 1;
-    }
-    return 0;
+        // MiniMLP on [x | xd | g] + residual (layers.py:229-239)
+        const float* in_ptr[3] = {x, w.xd, w.gf};
+        int in_w[3] = {C, C, C};
+        int nseg = p->with_grad ? 3 : 2;
+        for (int j = 0; j < p->n_mlp; ++j) {
+            const bool last = (j == p->n_mlp - 1);
+            float* dst = last ? out : (sv ? sv->h[j] : w.h[j & 1]);
+            F16 f;
+            if (f16) {
+                f = f16_of(j == 0 ? m.in_amax : sw + SW_H0 + j - 1, aw + AW_W0 + j, last ? p->out_amax : sw + SW_H0 + j);
+                if (j == 0) { f.a.p[1] = sw + SW_XD; f.a.c = p->with_grad ? 1.f : 0.f; }      // [x | xd | g], |g| = |tanh| <= 1
+            }
+            DN_CHECK(linear_fwd(mb, in_ptr, in_w, nseg, p->W[j], p->widths[j], p->b[j], p->widths[j + 1],
+                                last ? DN_EPI_BIAS_RESID : DN_EPI_BIAS_RELU, last ? nullptr : p->mask[j + 1],
+                                last ? x : nullptr, dst, st, last ? 0ull : layer_seed(p->drop_seed, j + 1), (const unsigned long long*)p->drop_seed_dev,
+                                f16_if(F16_MLP, f)));
+            in_ptr[0] = dst; in_w[0] = p->widths[j + 1]; nseg = 1;
+        }
+        return 0;
+    };
+    return chain ? chain_rows() : unfused_rows();
 }
 
+// ---- backward
+struct BlockBwdWs {
+    float *da[2], *d_xacc, *d_xd, *d_dots, *d_gx, *d_gy;      // d_a ping-pong [V, widest layer]; [V, C] each
+    float *part_w[DN_MAX_MLP_LAYERS], *part_b[DN_MAX_MLP_LAYERS], *part_a;      // TN partials + bias partials, one region per layer: the sums are deferred
+    DiffuseWs d;
+    float *psum, *aw, *chain;       // route.chain: the chained kernel's weight pieces
+};
+static BlockBwdWs block_bwd_layout(Bump& b, const dn_mesh_batch_t* mb, const dn_block_params_t* p, const BlockRoute& r) {
+    const int C = p->C;
+    const size_t VC = (size_t)mb->v_total * C;
+    BlockBwdWs w; memset(&w, 0, sizeof(w));
+    for (int i = 0; i < 2; ++i) w.da[i] = b.f((size_t)mb->v_total * max_width(p));
+    w.d_xacc = b.f(VC); w.d_xd = b.f(VC); w.d_dots = b.f(VC); w.d_gx = b.f(VC); w.d_gy = b.f(VC);
+    for (int j = 0; j < p->n_mlp; ++j) {
+        w.part_w[j] = b.f((size_t)mb->n_chunks * p->widths[j] * p->widths[j + 1]);
+        w.part_b[j] = b.f((size_t)mb->n_chunks * p->widths[j + 1]);
+    }
+    if (p->with_grad) w.part_a = b.f((size_t)mb->n_chunks * 4 * C * C);
+    w.d = diffuse_layout(b, mb, C, r.d, false, true);
+    w.psum = b.f((size_t)4 * C * C);
+    w.aw = b.f(AW_COUNT + DN_BLOCK_AMAX_WORDS + 2);
+    if (r.chain) w.chain = b.f((size_t)dn_chain_bwd_pieces(C, p->with_grad, p->with_rot, p->n_mlp) * (2 * (C / 16) * 64) * 4);
+    return w;
+}
 size_t dn_block_bwd_workspace_bytes(const dn_mesh_batch_t* mb, const dn_block_params_t* p) {
     if (!block_params_ok(p)) return 0;
-    const size_t VC = (size_t)mb->v_total * p->C;
-    size_t n = 2 * pad256((size_t)mb->v_total * max_width(p));     // d_a ping-pong
-    n += 5 * pad256(VC);                                            // d_xacc, d_xd, d_dots, d_gx, d_gy
-    for (int j = 0; j < p->n_mlp; ++j)                               // TN partials + bias partials, one region per layer: the sums
-        n += pad256((size_t)mb->n_chunks * p->widths[j] * p->widths[j + 1]) + pad256((size_t)mb->n_chunks * p->widths[j + 1]);   // are deferred
-    if (p->with_grad) n += pad256((size_t)mb->n_chunks * 4 * p->C * p->C);
-    n += pad256((size_t)mb->n_chunks * mb->k_eig * p->C);           // split-V partials of the diffusion backward
-    n += pad256((size_t)mb->n_mesh * mb->k_eig * p->C) + pad256((size_t)dn_spec_bwd_dt_rows(mb->n_mesh, mb->k_eig) * p->C);
-    n += pad256((size_t)4 * p->C * p->C) + amax_ws();
-    if (block_chain_ok(mb, p, 2)) n += pad256((size_t)dn_chain_bwd_pieces(p->C, p->with_grad, p->with_rot, p->n_mlp) * (2 * (p->C / 16) * 64) * 4);
-    if (diffuse_ok(mb, p->C)) n += pad256(diffuse_ws_floats(mb)) + pad256((size_t)diffuse_dt_rows(mb) * p->C);
-    return n + 512;
+    return ws_query([&](Bump& b) { block_bwd_layout(b, mb, p, block_route(mb, p, 2)); });
 }
 int dn_block_bwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, const float* x, const dn_block_saved_t* sv,
                      const float* d_out, const dn_block_grads_t* gr, void* ws, size_t ws_bytes, void* stream) {
     if (!block_params_ok(p) || !sv || !gr) return DN_ERR_INVALID;
     hipStream_t st = S(stream);
-    const int C = p->C, K = mb->k_eig;
-    const size_t VC = (size_t)mb->v_total * C;
+    const int C = p->C;
+    const BlockRoute r = block_route(mb, p, 2);
     Bump b(ws, ws_bytes);
-    float* da[2] = {b.f((size_t)mb->v_total * max_width(p)), b.f((size_t)mb->v_total * max_width(p))};
-    float* d_xacc = b.f(VC);
-    float* d_xd = b.f(VC);
-    float* d_dots = b.f(VC);
-    float* d_gx = b.f(VC);
-    float* d_gy = b.f(VC);
-    float* part_w[DN_MAX_MLP_LAYERS]; float* part_b[DN_MAX_MLP_LAYERS];
-    for (int j = 0; j < p->n_mlp; ++j) {
-        part_w[j] = b.f((size_t)mb->n_chunks * p->widths[j] * p->widths[j + 1]);
-        part_b[j] = b.f((size_t)mb->n_chunks * p->widths[j + 1]);
-    }
-    float* part_a = p->with_grad ? b.f((size_t)mb->n_chunks * 4 * C * C) : nullptr;
-    float* partial = b.f((size_t)mb->n_chunks * K * C);
-    float* dxs = b.f((size_t)mb->n_mesh * K * C);
-    float* dtp = b.f((size_t)dn_spec_bwd_dt_rows(mb->n_mesh, K) * C);
-    float* psum = b.f((size_t)4 * C * C);
-    float* aw = b.f(AW_COUNT + DN_BLOCK_AMAX_WORDS + 2);
-    float* chain_ws = block_chain_ok(mb, p, 2) ? b.f((size_t)dn_chain_bwd_pieces(C, p->with_grad, p->with_rot, p->n_mlp) * (2 * (C / 16) * 64) * 4) : nullptr;
-    float* diffuse_ws = diffuse_ok(mb, C) ? b.f(diffuse_ws_floats(mb)) : nullptr;
-    float* diffuse_dtp = diffuse_ok(mb, C) ? b.f((size_t)diffuse_dt_rows(mb) * C) : nullptr;
+    const BlockBwdWs w = block_bwd_layout(b, mb, p, r);
     if (!b.ok) return DN_ERR_INVALID;
-
-    // ---- operand magnitudes for the split-fp16 engine (the saved activations' words come from the forward)
-    const bool f16 = block_f16_ok(mb, p) && sv->amax;
+    float *aw = w.aw, *sw = sv->amax;      // call-local words; the saved activations' words (they come from the forward)
+    const bool f16 = r.f16 && sv->amax;
     // The parameter gradients (dW = d_a^T h, dA) are sums over ALL vertices with heavy cancellation: their error is the operand
     // precision times a condition number of ~1e3, and the two-term fp16 split carries 22 bits against fp32's 24 -- measured on the
     // trained-checkpoint golden: 2.9e-4 from fp64 where the fp32 reference itself is 0.8e-4 away.  They stay on the split-bf16
     // engine (24 bits); the row products (activations, input gradients: 128..384-term sums) take the split-fp16 one.
-    const bool wgrad_f16 = opt(O_F16_WGRAD) != 0;
-    const float* sw = sv->amax;
-    const float *dout_amax = nullptr, *ev_amax = nullptr;
-    // the chained backward kernel (dn_chain_bwd.hip) takes the row-local part -- MiniMLP input gradients, tanh', gradient-feature backward --
-    // under the conditions of the chained forward (two hidden-gradient buffers: MiniMLPs of up to three layers)
-    const bool chainb = block_chain_ok(mb, p, 2) && sv->amax && !wgrad_f16 && p->n_mlp <= 3 && chain_aligned(p, sv, x, d_out, gr->d_x) &&
-                        // (the chained backward does not record max |d_xd|: the diagnostic class that needs it keeps the unfused launches)
-                        !(block_f16_ok(mb, p) && (f16_mask() & F16_TOB_B) && !p->with_grad);
-    const bool words = f16 || chainb;
-    ChainPrepArgs pa; memset(&pa, 0, sizeof(pa));
-    int chain_np = 0;
-    if (words) {
-        AmaxInit in; memset(&in, 0, sizeof(in));
-        if (!chainb) {
-            if (p->with_grad) { in.jobs.push(p->A_re, (long long)C * C, aw + AW_WA); if (p->with_rot) in.jobs.push(p->A_im, (long long)C * C, aw + AW_WA); }
-            for (int j = 0; j < p->n_mlp && in.jobs.count < DN_AMAX_MAX_JOBS; ++j) in.jobs.push(p->W[j], (long long)p->widths[j] * p->widths[j + 1], aw + AW_W0 + j);
-        }
-        in.zero_range(aw, AW_WA);
-        in.zero_range(aw + AW_D0, DN_MAX_MLP_LAYERS + 1 + DN_BLOCK_AMAX_WORDS + 2);
-        if (f16) in.zero_range(gr->d_x_amax, 1);
-        if (chainb) {      // the weight-preparation kernel of the chained backward does this call's bookkeeping (one launch)
-            const int NK = C / 32;
-            auto piece = [&](const float* Wm, const float* Wm2, float* word, int ld, int row0, int T) {
-                ChainPrepPiece& q = pa.pc[chain_np++]; q.W = Wm; q.W2 = Wm2; q.amax = word; q.ld = ld; q.col0 = 32 * T; q.transposed = 1; q.row0 = row0; };
-            for (int j = p->n_mlp - 1; j >= 1; --j)
-                for (int T = 0; T < NK; ++T) piece(p->W[j], nullptr, aw + AW_W0 + j, C, 0, T);
-            for (int sg = 0; sg < (p->with_grad ? 3 : 2); ++sg)
-                for (int T = 0; T < NK; ++T) piece(p->W[0], nullptr, aw + AW_W0, p->widths[0], sg * C, T);
-            if (p->with_grad)
-                for (int rep = 0; rep < chain_hh(mb, true); ++rep)
-                    for (int T = 0; T < NK; ++T) {
-                        piece(p->A_re, p->with_rot ? p->A_im : nullptr, aw + AW_WA, C, 0, T);
-                        if (p->with_rot) piece(p->A_im, p->A_re, aw + AW_WA, C, 0, T);
-                    }
-            pa.out = reinterpret_cast<uint4*>(chain_ws);
-            for (int r = 0; r < in.nzero; ++r) pa.zero_range(in.zero[r], in.zero_n[r]);
-            DN_CHECK(dn_launch_chain_prep(pa, chain_np, C, st));
-        } else {
-            DN_CHECK(dn_launch_amax_init(in, st));
-        }
-        dout_amax = gr->d_out_amax;
-        ev_amax = mb->evecs_amax;
-        if (!dout_amax || (f16 && !ev_amax)) {
-            AmaxJobs jobs; jobs.count = 0;
-            if (!dout_amax) { jobs.push(d_out, (long long)VC, aw + AW_IN); dout_amax = aw + AW_IN; }
-            if (f16 && !ev_amax) { jobs.push(mb->evecs, (long long)mb->v_total * K, aw + AW_COUNT + DN_BLOCK_AMAX_WORDS); ev_amax = aw + AW_COUNT + DN_BLOCK_AMAX_WORDS; }
-            DN_CHECK(dn_launch_amax(jobs, st));
-        }
+    const bool wgrad_f16 = opt(O_F16_WGRAD) != 0, wf16 = f16 && wgrad_f16;
+    // the chained kernel under the conditions of the chained forward (two hidden-gradient buffers: MiniMLPs of up to three layers)
+    const bool chain = r.chain && sv->amax && !wgrad_f16 && p->n_mlp <= 3 && chain_aligned(p, sv, x, d_out, gr->d_x) &&
+                       // (the chained backward does not record max |d_xd|: the diagnostic class that needs it keeps the unfused launches)
+                       !(r.f16 && (f16_mask() & F16_TOB_B) && !p->with_grad);
+    // ---- magnitude words (with the chained kernel, its weight-preparation launch does this call's bookkeeping)
+    WordsFound m; memset(&m, 0, sizeof(m));
+    if (f16 || chain) {
+        const BlockWords bw = {d_out, gr->d_out_amax, aw + AW_IN, nullptr, {f16 ? gr->d_x_amax : nullptr, nullptr}, {1, 0}, false, false,
+                               chain ? w.chain : nullptr, r.hh};
+        DN_CHECK(block_words(mb, p, aw, f16, bw, st, m));
     }
-    auto W = [&](int j) { return (const float*)(aw + AW_W0 + j); };
-    auto D = [&](int j) { return aw + AW_D0 + j; };   // magnitude of d(pre-activation of layer j-1) = the d_a consumed by layer j-1; D(n_mlp) unused
-
-    // The fixed-order sums of the weight / bias / rotation-matrix partials are deferred: every product writes its partials to its
-    // own region and ONE launch reduces them all once the last one is written (5 launches -> 1 per block).
+    // ---- row work and weight gradients.  The fixed-order sums of the weight / bias / rotation-matrix partials are deferred: every product writes
+    // its partials to its own region and ONE launch reduces them all once the last one is written (5 launches -> 1 per block).
     MrJobs jobs; jobs.count = 0;
-    if (chainb) {
-        // ---- row-local gradients in one launch, then the weight-gradient products over what it wrote
+    // layer j's weight-gradient product dW_j = d_a^T in_j (in_0 = [x | xd | g], in_j = h_{j-1})
+    auto weight_grad = [&](int j, const float* d_a, const F16& f, TnBatch* tb) {
+        const float* ins[3] = {x, sv->xd, sv->g};
+        int iw[3] = {C, C, C}, nseg = p->with_grad ? 3 : 2;
+        if (j > 0) { ins[0] = sv->h[j - 1]; iw[0] = p->widths[j]; nseg = 1; }
+        return linear_bwd_weights(mb, d_a, p->widths[j + 1], ins, iw, nseg, gr->dW[j], gr->db[j], w.part_w[j], w.part_b[j], st, &jobs, f, tb);
+    };
+    auto grad_apply = [&]() {      // d_xd += gradX^T d_gx + gradY^T d_gy (in place)
+        return grad_apply_bwd(mb, w.d_gx, w.d_gy, w.d_xd, C, w.d_xd, st, (f16 && (f16_mask() & F16_TOB_B)) ? aw + AW_MISC : nullptr);
+    };
+    // chained: the kernel of dn_chain_bwd.hip takes the row-local part -- MiniMLP input gradients, tanh', gradient-feature backward -- in one
+    // launch; then the weight-gradient products over what it wrote
+    auto chain_rows = [&]() -> int {
         ChainBwdArgs cb; memset(&cb, 0, sizeof(cb));
         cb.d_out = d_out; cb.V = mb->v_total; cb.with_grad = p->with_grad; cb.with_rot = p->with_rot; cb.n_mlp = p->n_mlp;
         for (int j = 1; j < p->n_mlp; ++j) {
             cb.h[j - 1] = sv->h[j - 1];
             cb.dscale[j - 1] = (p->mask[j] || p->drop_seed) ? 2.f : 1.f;
-            cb.d_a[j - 1] = da[j & 1];
+            cb.d_a[j - 1] = w.da[j & 1];
         }
         cb.g = sv->g; cb.gx = sv->gx; cb.gy = sv->gy; cb.bre = sv->bre; cb.bim = sv->bim;
-        cb.wp = reinterpret_cast<const uint4*>(chain_ws);
+        cb.wp = reinterpret_cast<const uint4*>(w.chain);
         cb.wa_amax = aw + AW_WA;
         for (int j = 0; j < p->n_mlp; ++j) cb.w_amax[j] = aw + AW_W0 + j;
-        cb.d_out_amax = dout_amax;
-        cb.d_xacc = d_xacc; cb.d_xd = d_xd; cb.d_dots = d_dots; cb.d_gx = d_gx; cb.d_gy = d_gy;
-        DN_CHECK(dn_launch_chain_bwd(chain_np, cb, C, st, chain_hh(mb, true)));
+        cb.d_out_amax = m.in_amax;
+        cb.d_xacc = w.d_xacc; cb.d_xd = w.d_xd; cb.d_dots = w.d_dots; cb.d_gx = w.d_gx; cb.d_gy = w.d_gy;
+        DN_CHECK(dn_launch_chain_bwd(m.np, cb, C, st, r.hh));
         // every d_a exists now: the (up to three) weight-gradient products of the MiniMLP go out as ONE launch
         TnBatch tb;
-        const float* d_a = d_out;
-        for (int j = p->n_mlp - 1; j >= 0; --j) {
-            const int wo = p->widths[j + 1], wi = p->widths[j];
-            if (j > 0) {
-                const float* ins[1] = {sv->h[j - 1]};
-                const int iw[1] = {wi};
-                DN_CHECK(linear_bwd_weights(mb, d_a, wo, ins, iw, 1, gr->dW[j], gr->db[j], part_w[j], part_b[j], st, &jobs, F16(), &tb));
-                d_a = da[j & 1];
-            } else {
-                const float* ins[3] = {x, sv->xd, sv->g};
-                const int iw[3] = {C, C, C};
-                DN_CHECK(linear_bwd_weights(mb, d_a, wo, ins, iw, p->with_grad ? 3 : 2, gr->dW[0], gr->db[0], part_w[0], part_b[0], st, &jobs, F16(), &tb));
-            }
-        }
+        for (int j = p->n_mlp - 1; j >= 0; --j) DN_CHECK(weight_grad(j, j == p->n_mlp - 1 ? d_out : w.da[(j + 1) & 1], F16(), &tb));
         DN_CHECK(dn_launch_tngemm_multi(tb.g, tb.nchunks, tb.count, st));
-        if (p->with_grad) {
-            DN_CHECK(gradfeat_bwd_weights(mb, d_dots, sv->gx, sv->gy, C, gr->dA_re, p->with_rot ? gr->dA_im : nullptr, part_a, psum, st, &jobs));
-            DN_CHECK(grad_apply_bwd(mb, d_gx, d_gy, d_xd, C, d_xd, st, (f16 && (f16_mask() & F16_TOB_B)) ? aw + AW_MISC : nullptr));   // d_xd += gradX^T d_gx + gradY^T d_gy (in place)
-        }
-    } else {
+        if (!p->with_grad) return 0;
+        DN_CHECK(gradfeat_bwd_weights(mb, w.d_dots, sv->gx, sv->gy, C, gr->dA_re, p->with_rot ? gr->dA_im : nullptr, w.part_a, w.psum, st, &jobs));
+        return grad_apply();
+    };
+    auto unfused_rows = [&]() -> int {
+        auto W = [&](int j) { return (const float*)(aw + AW_W0 + j); };
+        auto D = [&](int j) { return aw + AW_D0 + j; };   // magnitude of d(pre-activation of layer j-1) = the d_a consumed by layer j-1; D(n_mlp) unused
         // ---- MiniMLP backward (autograd of layers.py:236); d_a = gradient w.r.t. a layer's pre-activation output
         const float* d_a = d_out;   // last layer has no activation; the residual branch is added into d_xacc below
-        const float* da_amax = dout_amax;
+        const float* da_amax = m.in_amax;
         for (int j = p->n_mlp - 1; j >= 0; --j) {
             const int wo = p->widths[j + 1], wi = p->widths[j];
+            F16 fw;
+            if (wf16 && j > 0) fw = f16_of(da_amax, sw + SW_H0 + j - 1);
+            else if (wf16) { fw = f16_of(da_amax, sw + SW_X); fw.b.p[1] = sw + SW_XD; fw.b.c = p->with_grad ? 1.f : 0.f; }
+            DN_CHECK(weight_grad(j, d_a, fw, nullptr));
             if (j > 0) {
-                const float* ins[1] = {sv->h[j - 1]};
-                const int iw[1] = {wi};
-                DN_CHECK(linear_bwd_weights(mb, d_a, wo, ins, iw, 1, gr->dW[j], gr->db[j], part_w[j], part_b[j], st, &jobs,
-                                            (f16 && wgrad_f16) ? f16_of(da_amax, sw + SW_H0 + j - 1) : F16()));
-                float* nxt = da[j & 1];
+                float* nxt = w.da[j & 1];
                 // d(pre-act of layer j-1) = (d_a W_j) * relu'(.) * dropout scale; h>0 <=> kept and active
                 DN_CHECK(linear_bwd_input(mb, d_a, wo, p->W[j], wi, 0, wi, DN_EPI_MUL_DFAC, sv->h[j - 1],
                                           (p->mask[j] || p->drop_seed) ? 2.f : 1.f, nxt, st, f16 ? f16_if(F16_LBI, f16_of(da_amax, W(j), D(j))) : F16()));
                 d_a = nxt; da_amax = D(j);
-            } else {
-                const float* ins[3] = {x, sv->xd, sv->g};
-                const int iw[3] = {C, C, C};
-                F16 fw;
-                if (f16 && wgrad_f16) { fw = f16_of(da_amax, sw + SW_X); fw.b.p[1] = sw + SW_XD; fw.b.c = p->with_grad ? 1.f : 0.f; }
-                DN_CHECK(linear_bwd_weights(mb, d_a, wo, ins, iw, p->with_grad ? 3 : 2, gr->dW[0], gr->db[0], part_w[0], part_b[0], st, &jobs, fw));
-                // d_h0 = d_a W_0 split into its column groups [x | xd | g]
-                const F16 fi = f16 ? f16_if(F16_LBI, f16_of(da_amax, W(0))) : F16();
-                DN_CHECK(linear_bwd_input(mb, d_a, wo, p->W[0], wi, 0, C, DN_EPI_ADD, d_out, 1.f, d_xacc, st, fi));       // + residual
-                F16 fxd = fi; if (f16 && !p->with_grad) fxd.o = aw + AW_MISC;     // without gradient features this IS the d_xd the diffusion backward reads
-                DN_CHECK(linear_bwd_input(mb, d_a, wo, p->W[0], wi, C, C, DN_EPI_STORE, nullptr, 1.f, d_xd, st, fxd));
-                if (p->with_grad) {
-                    F16 fd = fi; if (f16) fd.o = D(0);                             // D(0): magnitude of d_dots
-                    DN_CHECK(linear_bwd_input(mb, d_a, wo, p->W[0], wi, 2 * C, C, DN_EPI_DTANH, sv->g, 1.f, d_dots, st, fd));
-                }
+                continue;
+            }
+            // d_h0 = d_a W_0 split into its column groups [x | xd | g]
+            const F16 fi = f16 ? f16_if(F16_LBI, f16_of(da_amax, W(0))) : F16();
+            DN_CHECK(linear_bwd_input(mb, d_a, wo, p->W[0], wi, 0, C, DN_EPI_ADD, d_out, 1.f, w.d_xacc, st, fi));       // + residual
+            F16 fxd = fi; if (f16 && !p->with_grad) fxd.o = aw + AW_MISC;     // without gradient features this IS the d_xd the diffusion backward reads
+            DN_CHECK(linear_bwd_input(mb, d_a, wo, p->W[0], wi, C, C, DN_EPI_STORE, nullptr, 1.f, w.d_xd, st, fxd));
+            if (p->with_grad) {
+                F16 fd = fi; if (f16) fd.o = D(0);                             // D(0): magnitude of d_dots
+                DN_CHECK(linear_bwd_input(mb, d_a, wo, p->W[0], wi, 2 * C, C, DN_EPI_DTANH, sv->g, 1.f, w.d_dots, st, fd));
             }
         }
+        if (!p->with_grad) return 0;
         // ---- gradient features + gradient apply backward
-        if (p->with_grad) {
-            const float* A_im = p->with_rot ? p->A_im : nullptr;
-            DN_CHECK(gradfeat_bwd_weights(mb, d_dots, sv->gx, sv->gy, C, gr->dA_re, p->with_rot ? gr->dA_im : nullptr, part_a, psum, st, &jobs,
-                                          (f16 && wgrad_f16) ? D(0) : nullptr, (f16 && wgrad_f16) ? sw + SW_G : nullptr));
-            F16 fg;
-            if (f16) { fg = f16_of(D(0), aw + AW_WA); fg.a.mul = sw + SW_G; }     // A = d_dots * (gx | gy)
-            DN_CHECK(gradfeat_bwd_inputs(mb, d_dots, sv->gx, sv->gy, sv->bre, sv->bim, p->A_re, A_im, C, d_gx, d_gy, st, f16_if(F16_GFB, fg)));
-            DN_CHECK(grad_apply_bwd(mb, d_gx, d_gy, d_xd, C, d_xd, st, (f16 && (f16_mask() & F16_TOB_B)) ? aw + AW_MISC : nullptr));   // d_xd += gradX^T d_gx + gradY^T d_gy (in place)
-        }
-    }
-    // ---- diffusion backward: one persistent launch (3-term engine throughout) when the batch carries its plan; its d_t rows join the block's
-    // deferred gradient sums
-    if (diffuse_ws && !(f16 && (f16_mask() & F16_TOB_B)) && diffuse_aligned(d_xd, gr->d_x, sv->xs, mb->evecs, p->time, d_xacc)) {
-        DfLaunch L = diffuse_new(mb, diffuse_ws);
-        L.bwd = 1; L.x = d_xd; L.time = p->time; L.xs = sv->xs; L.out = gr->d_x; L.add = d_xacc; L.dt_part = diffuse_dtp;
-        L.out_amax = f16 ? gr->d_x_amax : nullptr;
-        DN_CHECK(dn_launch_diffuse(L, st));
-        if (!jobs.push(diffuse_dtp, diffuse_dt_rows(mb), C, gr->d_time))
-            DN_CHECK(dn_launch_reduce(diffuse_dtp, gr->d_time, diffuse_dt_rows(mb), C, C, st));
-        return dn_launch_multi_reduce(jobs, st);          // every parameter gradient of the block: one fixed-order reduction launch
-    }
-    DN_CHECK(to_basis_partials(mb, d_xd, C, false, partial, st, f16 ? f16_if(F16_TOB_B, f16_of(ev_amax, aw + AW_MISC)) : F16()));
-    if (dn_spec_bwd_fused_ok(partial, p->time, sv->xs, dxs, dtp, C)) {
-        // one launch: per-mesh sums of the partials, exp(-lambda t), d_t contributions; their sum over (mesh, eigenvalue group) joins the block's
-        // other deferred gradient sums below
-        DN_CHECK(dn_launch_spec_bwd_fused(partial, mb->mesh_chunk_off, mb->evals, p->time, sv->xs, dxs, dtp, mb->n_mesh, K, C, st, f16 ? aw + AW_YS : nullptr));
-        if (!jobs.push(dtp, dn_spec_bwd_dt_rows(mb->n_mesh, K), C, gr->d_time))
-            DN_CHECK(dn_launch_reduce(dtp, gr->d_time, dn_spec_bwd_dt_rows(mb->n_mesh, K), C, C, st));
-    } else {
-        DN_CHECK(dn_launch_seg_reduce(partial, mb->mesh_chunk_off, mb->n_mesh, 0, dxs, (long long)K * C, st));
-        DN_CHECK(dn_launch_spec_bwd(dxs, mb->evals, p->time, sv->xs, dtp, mb->n_mesh, K, C, st, f16 ? aw + AW_YS : nullptr));
-        DN_CHECK(dn_launch_reduce(dtp, gr->d_time, mb->n_mesh, C, C, st));
-    }
-    DN_CHECK(dn_launch_multi_reduce(jobs, st));       // every parameter gradient of the block: one fixed-order reduction launch
-    return from_basis(mb, dxs, C, gr->d_x, d_xacc, true, st, f16 ? f16_if(F16_FROMB_B, f16_of(ev_amax, aw + AW_YS, gr->d_x_amax)) : F16());
+        DN_CHECK(gradfeat_bwd_weights(mb, w.d_dots, sv->gx, sv->gy, C, gr->dA_re, p->with_rot ? gr->dA_im : nullptr, w.part_a, w.psum, st, &jobs,
+                                      wf16 ? D(0) : nullptr, wf16 ? sw + SW_G : nullptr));
+        F16 fg;
+        if (f16) { fg = f16_of(D(0), aw + AW_WA); fg.a.mul = sw + SW_G; }     // A = d_dots * (gx | gy)
+        DN_CHECK(gradfeat_bwd_inputs(mb, w.d_dots, sv->gx, sv->gy, sv->bre, sv->bim, p->A_re, p->with_rot ? p->A_im : nullptr, C, w.d_gx, w.d_gy, st, f16_if(F16_GFB, fg)));
+        return grad_apply();
+    };
+    DN_CHECK(chain ? chain_rows() : unfused_rows());
+    // ---- diffusion backward: its d_t rows join the deferred sums, which go out there
+    F16 tob, fromb;
+    if (f16) { tob = f16_if(F16_TOB_B, f16_of(m.ev_amax, aw + AW_MISC)); fromb = f16_if(F16_FROMB_B, f16_of(m.ev_amax, aw + AW_YS, gr->d_x_amax)); }
+    return diffuse_bwd(mb, r.d, w.d, w.d_xd, sv->xs, p->time, C, w.d_xacc, gr->d_x, gr->d_time, st, !(f16 && (f16_mask() & F16_TOB_B)), tob, fromb,
+                       f16 ? aw + AW_YS : nullptr, &jobs);
 }
 
 // ------------------------------------------------------------------ head / loss next to the path (dn_head.hip)
 #define DN_HEAD_BLOCKS 2048
-size_t dn_head_workspace_bytes(void) { return pad256(2 * DN_HEAD_BLOCKS) + 512; }
+static float* head_layout(Bump& b) { return b.f(2 * DN_HEAD_BLOCKS); }
+size_t dn_head_workspace_bytes(void) {
+    return ws_query([&](Bump& b) { head_layout(b); });
+}
 int dn_head_fwd_f32(const float* x, int n_src, int C, const int32_t* rowptr, const int32_t* col, int n_out, float div, int log_softmax,
                     const int64_t* labels, float smoothing, float* logp, float* loss, float* count, void* ws, size_t ws_bytes, void* stream) {
     if (!x || n_src < 0 || n_out < 0 || C <= 0 || (rowptr && !col) || div <= 0.f || (labels && (!loss || !count))) return DN_ERR_INVALID;
     if (!rowptr && n_out != n_src) return DN_ERR_INVALID;
     Bump b(ws, ws_bytes);
-    float* partial = b.f(2 * DN_HEAD_BLOCKS);
+    float* partial = head_layout(b);
     if (!b.ok) return DN_ERR_INVALID;
     HeadArgs a; memset(&a, 0, sizeof(a));
     a.x = x; a.ldx = C; a.rowptr = rowptr; a.col = col; a.inv_div = 1.f / div; a.labels = (const long long*)labels; a.smoothing = smoothing;
@@ -1163,7 +1152,10 @@ int dn_hks_f32(const float* evals, const float* evecs, const float* scales, int 
 }
 
 // ------------------------------------------------------------------ operator packing
-size_t dn_coo_to_csr_workspace_bytes(int64_t nnz, int n_cols) { return dn_pack_ws_bytes(nnz, n_cols) + 512; }
+static int* coo_layout(Bump& b, int64_t nnz, int n_cols) { return (int*)b.f((size_t)n_cols + 1 + (size_t)nnz); }      // = dn_pack_ws_bytes()
+size_t dn_coo_to_csr_workspace_bytes(int64_t nnz, int n_cols) {
+    return ws_query([&](Bump& b) { coo_layout(b, nnz, n_cols); });
+}
 int dn_coo_to_csr_i64(const int64_t* rows, int row_div, const int64_t* cols, const float* vx, const float* vy, int64_t nnz, int n_rows, int n_cols,
                       int32_t* rowptr, int32_t* col, int32_t* t_rowptr, int32_t* t_col, float* t_vx, float* t_vy, int32_t* status,
                       void* ws, size_t ws_bytes, void* stream) {
@@ -1171,7 +1163,7 @@ int dn_coo_to_csr_i64(const int64_t* rows, int row_div, const int64_t* cols, con
         (nnz > 0 && (!cols || !col || !t_col || (vx && !t_vx) || (vy && !t_vy))))
         return DN_ERR_INVALID;
     Bump b(ws, ws_bytes);
-    int* w = (int*)b.f((size_t)n_cols + 1 + (size_t)nnz);
+    int* w = coo_layout(b, nnz, n_cols);
     if (!b.ok) return DN_ERR_INVALID;
     return dn_launch_coo_to_csr((const long long*)rows, row_div, (const long long*)cols, vx, vy, nnz, n_rows, n_cols, rowptr, col, t_rowptr, t_col,
                                 t_vx, t_vy, status, w, S(stream));

@@ -71,10 +71,7 @@ __global__ __launch_bounds__(1024) void chain_prep_kernel(ChainPrepArgs a) {
     __shared__ float red[NTHR];
     const int tid = threadIdx.x;
     if ((int)blockIdx.x >= a.npieces) {          // start-of-call bookkeeping
-        for (int r = 0; r < a.nzero; ++r)
-            for (int i = tid; i < a.zero_n[r]; i += NTHR) a.zero[r][i] = 0.f;
-        if (tid == 0 && a.copy_src && a.copy_dst) *a.copy_dst = *a.copy_src;
-        for (int i = tid; i < a.clamp_n; i += NTHR) { const float v = a.clamp_p[i]; a.clamp_p[i] = v < a.clamp_min ? a.clamp_min : v; }   // (NaN stays NaN, as torch.clamp)
+        dn_call_prep<NTHR>(a.prep, tid);
         return;
     }
     const ChainPrepPiece pc = a.pc[blockIdx.x];

@@ -469,6 +469,21 @@ enum { DN_SP_FWD2 = 0, DN_SP_BWD2 = 1, DN_SP_ONE = 2 };
 // ---------------------------------------------------------------------------------------
 #define DN_CH_LAYERS 4   // MiniMLP depth the chained kernel takes (the default net has 3); deeper nets use the unfused path
 
+// Start-of-call bookkeeping of a block call, executed by one workgroup of its first launch (amax_init_kernel, or chain_prep_kernel on the
+// chained path): up to four word ranges zeroed, one word copied, clamp_p[0..clamp_n) raised to >= clamp_min in place (the diffusion times,
+// layers.py:48-49)
+struct CallPrep {
+    float* zero[4]; int zero_n[4]; int nzero; const float* copy_src; float* copy_dst;
+    float* clamp_p; int clamp_n; float clamp_min;
+    void zero_range(float* p, int n) { if (p && n > 0 && nzero < 4) { zero[nzero] = p; zero_n[nzero] = n; ++nzero; } }
+};
+template <int NTHR>
+__device__ __forceinline__ void dn_call_prep(const CallPrep& a, int tid) {
+    for (int r = 0; r < a.nzero; ++r)
+        for (int i = tid; i < a.zero_n[r]; i += NTHR) a.zero[r][i] = 0.f;
+    if (tid == 0 && a.copy_src && a.copy_dst) *a.copy_dst = *a.copy_src;
+    for (int i = tid; i < a.clamp_n; i += NTHR) { const float v = a.clamp_p[i]; a.clamp_p[i] = v < a.clamp_min ? a.clamp_min : v; }   // (NaN stays NaN, as torch.clamp)
+}
 struct ChainPrepPiece {
     const float* W;      // [C, ld] row-major (nn.Linear layout: W[out][in])
     const float* W2;     // optional second matrix of the same shape sharing the magnitude word (A_re / A_im)
@@ -483,11 +498,7 @@ struct ChainPrepArgs {
     ChainPrepPiece pc[DN_CH_MAX_PIECES];
     uint4* out;          // [npieces][2 * (C / 16) * 64]
     int npieces;
-    // start-of-call bookkeeping done by the workgroup behind the last piece (what dn_launch_amax_init does for the unfused path):
-    // word ranges zeroed, one word copied
-    float* zero[4]; int zero_n[4]; int nzero; const float* copy_src; float* copy_dst;
-    float* clamp_p; int clamp_n; float clamp_min;       // as AmaxInit's
-    void zero_range(float* p, int n) { if (p && n > 0 && nzero < 4) { zero[nzero] = p; zero_n[nzero] = n; ++nzero; } }
+    CallPrep prep;       // start-of-call bookkeeping done by the workgroup behind the last piece (what dn_launch_amax_init does for the unfused path)
 };
 struct ChainArgs {
     // gradient operators (shared CSR pattern, two value arrays) and the dense inputs
@@ -624,11 +635,9 @@ int dn_launch_spec_bwd(float* dys_inplace, const float* evals, const float* time
 struct AmaxJobs { const float* src[DN_AMAX_MAX_JOBS]; long long n[DN_AMAX_MAX_JOBS]; float* dst[DN_AMAX_MAX_JOBS]; int count;
     void push(const float* s, long long len, float* d) { if (s && d && len > 0 && count < DN_AMAX_MAX_JOBS) { src[count] = s; n[count] = len; dst[count] = d; ++count; } } };
 int dn_launch_amax(const AmaxJobs& jobs, hipStream_t stream);
-// one-launch start of a block call: stored maxima of small tensors (jobs with the same destination must be adjacent), zeroing of up to
-// four word ranges, one word copy
-struct AmaxInit { AmaxJobs jobs; int same[DN_AMAX_MAX_JOBS]; float* zero[4]; int zero_n[4]; int nzero; const float* copy_src; float* copy_dst;
-    float* clamp_p; int clamp_n; float clamp_min;       // clamp_p[0..clamp_n) raised to >= clamp_min in place (the diffusion times, layers.py:48-49)
-    void zero_range(float* p, int n) { if (p && n > 0 && nzero < 4) { zero[nzero] = p; zero_n[nzero] = n; ++nzero; } } };
+// one-launch start of a block call: stored maxima of small tensors (jobs with the same destination must be adjacent) and the call's
+// bookkeeping (CallPrep)
+struct AmaxInit { AmaxJobs jobs; int same[DN_AMAX_MAX_JOBS]; CallPrep prep; };
 int dn_launch_amax_init(const AmaxInit& a, hipStream_t stream);
 int dn_launch_reduce(const float* partial, float* out, int n, long long stride, long long len, hipStream_t stream);
 // out[s][i] = sum_{ch in [seg_off[s], seg_off[s+1])} partial[ch][i]  (seg_off == nullptr: one segment [0,n))

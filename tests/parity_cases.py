@@ -648,6 +648,55 @@ def run_ops(device, sizes=(200, 77), K=20, C=32, seed=5, chunk_rows=None):
     assert helpers.rel_l2(xm.grad.cpu(), xr.grad) < GRAD_TOL
 
 
+def run_exact_workspace(device):
+    """Every *_workspace_bytes() query against the call it sizes (csrc/dn_api.hip runs ONE layout function for both).
+    Enough: existing cases, one per route of the block and the per-op entry points, with ``ops._ws`` replaced by one that hands every call a
+    fresh buffer starting 16 bytes past a 256-byte boundary and passes exactly the queried byte count.
+    Not more than enough: the three calls whose query is theirs alone (training forward, inference forward, backward) must refuse, with
+    hipErrorInvalidValue and before any launch, a 256-byte aligned buffer of query - 768 bytes: the regions sum to query - 512, and an aligned
+    start consumes none of the slack."""
+    def exact_ws(mb, nbytes):
+        nbytes = int(nbytes)
+        raw = torch.empty(max(nbytes, 1024) + 512, dtype=torch.uint8, device=mb.device)
+        return raw[(-raw.data_ptr()) % 256 + 16:], nbytes
+
+    def tight_ws(mb, nbytes):
+        raw = torch.empty(int(nbytes) + 512, dtype=torch.uint8, device=mb.device)
+        return raw[(-raw.data_ptr()) % 256:], int(nbytes) - 768
+
+    real_ws = ops._ws
+    ops._ws = exact_ws
+    try:
+        run_ragged_net(device, sizes=(150, 130), K=128, C=128, N_block=1, chunk_rows=64)      # chained forward and backward, direct back-projection
+        run_ragged_net(device, sizes=(130, 257, 64), chunk_rows=64)                            # unfused launches, C = 32, no split-fp16
+        run_spectral_grad(device, sizes=(150, 193), N_block=1, dropout=False, chain_nw=2)      # spectral-gradient form and its reference form
+        run_diffuse_fused(device, sizes=(130, 700), seed=9, configs=((2, 0, 1),), reps=1)      # one-launch diffusion
+        run_ragged_net(device, sizes=(70, 45), K=32, C=256, N_block=1, empty_grad_rows=3, chunk_rows=64)      # C = 256 forward
+        run_ops(device)                                                                        # the per-op entry points
+
+        # the tight side, on the first case's batch
+        C, seed = 128, 3
+        meshes, _ = make_ragged((150, 130), 128, 3, seed)
+        mb = pack(meshes, device, chunk_rows=64)
+        g = torch.Generator().manual_seed(seed)
+        rnd = lambda *shape: (torch.randn(*shape, generator=g) / shape[-1] ** 0.5).to(device)
+        cfg = ops.BlockConfig(C, [3 * C, C, C, C], True, True)
+        x, time, A_re, A_im = rnd(mb.v_total, C), torch.rand(C, generator=g).to(device) + 0.1, rnd(C, C), rnd(C, C)
+        Ws, bs = [rnd(cfg.widths[i + 1], cfg.widths[i]) for i in range(3)], [rnd(cfg.widths[i + 1]) for i in range(3)]
+        args = (mb, cfg, None, x, time, A_re, A_im, Ws, bs)
+        grads = [torch.empty_like(t) for t in (time, A_re, A_im)] + [torch.empty_like(t) for wb in zip(Ws, bs) for t in wb]
+        out, saved, _ = ops.block_fwd(*args, save=True)
+        ops.block_fwd(*args, save=False)
+        ops.block_bwd(mb, cfg, None, torch.ones_like(out), *args[3:], saved, grads)
+        ops._ws = tight_ws
+        for call in (lambda: ops.block_fwd(*args, save=True), lambda: ops.block_fwd(*args, save=False),
+                     lambda: ops.block_bwd(mb, cfg, None, torch.ones_like(out), *args[3:], saved, grads)):
+            with pytest.raises(RuntimeError, match=r"hipError 1$"):
+                call()
+    finally:
+        ops._ws = real_ws
+
+
 def run_backproject_wide(device, sizes=(300, 257, 290), seed=17, tol=4e-6):
     """K = C = 256 (BASELINE config 4's shape): the forward back-projection runs as the ring kernel of dn_backproject_wide.hip (3-term engine, the
     spectrum split once per mesh and streamed through LDS).  LearnedTimeDiffusion forward against the fp64 evaluation of layers.py:44-67 and

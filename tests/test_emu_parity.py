@@ -44,6 +44,11 @@ def test_ops_on_emulator(emu):
     parity_cases.run_ops(emu, sizes=(300, 277, 170), K=160, C=192, seed=3)   # 2 x 2 output tiles per chunk block: the one-dimensional XCD-ordered launch of the split-V products, ragged tile edges
 
 
+def test_exact_workspace_on_emulator(emu):
+    import parity_cases
+    parity_cases.run_exact_workspace(emu)
+
+
 @pytest.mark.parametrize("outputs_at", ["vertices", "faces", "global_mean"])
 def test_ragged_batch_on_emulator(emu, outputs_at):
     import parity_cases

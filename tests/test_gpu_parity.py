@@ -44,6 +44,11 @@ def test_single_ops(dev):
     parity_cases.run_ops(dev, sizes=(9000, 300), K=256, C=256, seed=4)
 
 
+def test_exact_workspace(dev):
+    import parity_cases
+    parity_cases.run_exact_workspace(dev)
+
+
 def test_one_launch_diffusion(dev):
     """dn_diffuse.hip on the device (256 co-resident workgroups, real inter-workgroup hand-offs): forward + backward against the oracle and the
     three-launch form for 1-4 mesh groups, both schedules, deferred / immediate arrivals, the forced solo path (bit for bit the cooperative
