@@ -474,7 +474,7 @@ int dn_get_option(const char* name, int* value) {
     return DN_ERR_INVALID;
 }
 
-int dn_version(void) { return 600; }
+int dn_version(void) { return 700; }
 int dn_tile_rows(void) { return DN_TM; }
 int dn_tn_target_chunks(void) { return 2 * dn_num_cus(); }
 int dn_tn_target_chunks_k(int k_eig) { return (k_eig >= 256 ? 1 : 2) * dn_num_cus(); }
@@ -921,6 +921,7 @@ int dn_block_fwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, cons
                 ca.mask[j] = p->mask[j + 1];
                 ca.seed[j] = p->mask[j + 1] ? 0ull : layer_seed(p->drop_seed, j + 1);
                 ca.h[j] = sv ? sv->h[j] : nullptr;
+                ca.hbits[j] = (sv && C < 256) ? sv->hbits[j] : nullptr;      // (sign-bit words exist at C = 64, 128)
                 ca.h_amax[j] = sw + SW_H0 + j;
             }
         }
@@ -940,7 +941,12 @@ int dn_block_fwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, cons
             ca.ysp = reinterpret_cast<const uint4*>(w.ysp); ca.ys_amax = w.ysa;
             ca.xd_out = (sv || C >= 256) ? w.xd : nullptr; ca.xd_amax_out = sw + SW_XD;
         }
-        return dn_launch_chain_fwd(m.np, ca, C, st, r.hh);
+        DN_CHECK(dn_launch_chain_fwd(m.np, ca, C, st, r.hh));
+        // the sign-bit words where the kernel's wave shape does not form them itself (C = 128, two halves per wave): one pass over the stored h_j
+        if (sv && (C == 64 || C == 128) && !dn_chain_fwd_writes_hbits(C, r.hh))
+            for (int j = 0; j < p->n_mlp - 1; ++j)
+                if (sv->hbits[j]) DN_CHECK(dn_launch_hbits_pack(sv->h[j], sv->hbits[j], mb->v_total, C, st));
+        return 0;
     };
     // ---- row work, unfused
     auto unfused_rows = [&]() -> int {
@@ -966,6 +972,9 @@ int dn_block_fwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, cons
                                 last ? DN_EPI_BIAS_RESID : DN_EPI_BIAS_RELU, last ? nullptr : p->mask[j + 1],
                                 last ? x : nullptr, dst, st, last ? 0ull : layer_seed(p->drop_seed, j + 1), (const unsigned long long*)p->drop_seed_dev,
                                 f16_if(F16_MLP, f)));
+            // the saved set's sign-bit words of h_j (the chained kernel forms them in its epilogue): one small pass over what was just stored
+            if (!last && sv && sv->hbits[j] && (C == 64 || C == 128) && p->widths[j + 1] == C)
+                DN_CHECK(dn_launch_hbits_pack(dst, sv->hbits[j], mb->v_total, C, st));
             in_ptr[0] = dst; in_w[0] = p->widths[j + 1]; nseg = 1;
         }
         return 0;
@@ -1048,6 +1057,7 @@ int dn_block_bwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, cons
         cb.d_out = d_out; cb.V = mb->v_total; cb.with_grad = p->with_grad; cb.with_rot = p->with_rot; cb.n_mlp = p->n_mlp;
         for (int j = 1; j < p->n_mlp; ++j) {
             cb.h[j - 1] = sv->h[j - 1];
+            cb.hbits[j - 1] = sv->hbits[j - 1];      // all set: the kernel reads the sign-bit words and leaves h to the weight-gradient products
             cb.dscale[j - 1] = (p->mask[j] || p->drop_seed) ? 2.f : 1.f;
             cb.d_a[j - 1] = w.da[j & 1];
         }

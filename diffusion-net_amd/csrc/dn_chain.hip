@@ -169,6 +169,7 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
     constexpr int NTHR = 64 * NW;
     constexpr int PIECE = 2 * NT * 64;    // uint4 per piece
     constexpr int LPT = PIECE / NTHR;     // DMA requests per thread and piece
+    constexpr bool HBW = C < 256 && !(C == 128 && HH == 2);      // this instantiation forms the sign-bit words of h_j (dn_chain_fwd_writes_hbits)
     constexpr bool G0 = C >= 256;         // the one-wave-per-SIMD form of C = 256 (see the gradient-feature stage)
     constexpr int RING = DN_CH_RING;      // (C = 256: 32 KiB pieces; 128 KiB of ring + 32 KiB of gather slices are the CU's 160 KiB)
     constexpr int GCH = DN_CH_GCHUNK;
@@ -888,6 +889,33 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
                     for (int hh = 0; hh < HH; ++hh)
                         ch_st_tiles<NT, HH == 1>(hj, C, rowh[hh], row_end, m, q, [&](const int nt) { return make_float4(acc[hh][nt][0], acc[hh][nt][1], acc[hh][nt][2], acc[hh][nt][3]); });
                 }
+                // The signs of h_j as one word per lane and half (dn_block_saved_t.hbits: all the chained backward needs of h_j), from this lane's own
+                // values: bit 4 nt + e of word (row, q) <=> h_j[row][16 nt + 4 q + e] > 0; a wave's 16 rows are 256 contiguous bytes.
+                // Not in the two-half form of C = 128 (dn_chain_fwd_writes_hbits): that kernel spills 50-54 registers as it is and every placement
+                // of these lines tried added 5-10 more; its route (beyond 262 144 rows, or option chain_hh = 2) takes the pack pass over the stored h_j.
+                // Measured at 300k rows (profiles/hbits_ab.txt): the pass costs the block forward +53 us, the backward gains 26 us: that route loses ~1 %.
+                if constexpr (HBW) {
+                    if (unsigned* hb = a.hbits[j]) {
+#pragma unroll
+                        for (int hh = 0; hh < HH; ++hh) {
+                            unsigned w = 0u;
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt) {
+                                unsigned nib = 0u;
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) nib |= (acc[hh][nt][e] > 0.f ? 1u : 0u) << e;
+#ifndef DN_EMULATE
+                                // (the nibble as a register value: folded into the word's position, every bit becomes a select of the constant
+                                // 1 << (4 nt + e), and the 25 of them that are no inline constants stay in registers across the whole kernel:
+                                // +10 registers, 8 of them spilled in the one-half form of C = 128)
+                                asm volatile("" : "+v"(nib));
+#endif
+                                w |= nib << (4 * nt);
+                            }
+                            if (liveh[hh]) hb[(long long)rowh[hh] * 4 + q] = w;
+                        }
+                    }
+                }
                 wm = ch_wave_max(wm);
 #pragma unroll
                 for (int jj = 0; jj < DN_CH_LAYERS; ++jj) hmax[jj] = (jj == j && wm > hmax[jj]) ? wm : hmax[jj];   // (no dynamic register index)
@@ -1037,6 +1065,7 @@ int dn_chain_pieces(int C, int with_grad, int with_rot, int n_mlp) {
 size_t dn_chain_ws_bytes(int C, int with_grad, int with_rot, int n_mlp) {
     return (size_t)dn_chain_pieces(C, with_grad, with_rot, n_mlp) * (2 * (C / 16) * 64) * sizeof(uint4);
 }
+bool dn_chain_fwd_writes_hbits(int C, int hh) { return (C == 64 || C == 128) && !(C == 128 && hh == 2); }
 bool dn_chain_sg_eligible(int C, int K, int with_grad, int hh) {
     return with_grad && (((C == 128 || C == 64) && K == 128 && hh == 1) || (C == 256 && K == 256 && hh == 2));
 }
@@ -1139,11 +1168,13 @@ int dn_launch_chain_fwd(int npieces, const ChainArgs& a, int C, hipStream_t stre
         double nw = 1.0;                                     // out
         if (a.gx) nw += 2.0; if (a.bre) nw += 2.0; if (a.g) nw += 1.0;
         if (a.sg_pack && a.xd_out) nw += 1.0;
-        for (int j = 0; j < DN_CH_LAYERS; ++j) if (j < a.n_mlp - 1 && a.h[j]) nw += 1.0;
+        for (int j = 0; j < DN_CH_LAYERS - 1; ++j) if (j < a.n_mlp - 1 && a.h[j]) nw += 1.0;
         const double prod = (a.with_grad ? (a.with_rot ? 4.0 : 2.0) : 0.0) + (a.with_grad ? 3.0 : 2.0) + (a.n_mlp - 1);
         const double Ksg = a.sg_pack ? (C >= 256 ? 256.0 : 128.0) : 0.0;
         const double rd = a.sg_pack ? VC + 3.0 * 4.0 * (double)a.V * Ksg + (C >= 256 ? VC : 0.0) : 2.0 * VC;      // (C = 256: xd written and read back)
-        dn_prof_end(DN_K_CHAIN, stream, 2.0 * (double)a.V * C * C * prod + 3.0 * 2.0 * (double)a.V * Ksg * C, rd + VC * nw + (a.sg_pack && C >= 256 && !a.gx ? VC : 0.0));
+        double hb = 0.0;                                     // sign-bit words: 16 bytes per row and hidden layer
+        for (int j = 0; j < DN_CH_LAYERS - 1; ++j) if (dn_chain_fwd_writes_hbits(C, hh) && j < a.n_mlp - 1 && a.hbits[j]) hb += 16.0 * (double)a.V;
+        dn_prof_end(DN_K_CHAIN, stream, 2.0 * (double)a.V * C * C * prod + 3.0 * 2.0 * (double)a.V * Ksg * C, rd + VC * nw + hb + (a.sg_pack && C >= 256 && !a.gx ? VC : 0.0));
     }
     return err;
 }

@@ -16,8 +16,11 @@
 #include "dn_chain_tiles.h"
 #include <stdlib.h>
 
+// HB: relu'(h_j) comes from the sign-bit words the forward left (ChainBwdArgs.hbits: one dword per lane, half and layer, requested ahead of
+// the layer's product) and not from h_j itself -- [V, C] fp32 per hidden layer fetched, and HH x NT float4 of staging registers, for one bit per
+// element.  Same predicate on the same value: the results are bit-identical.
 DN_CLK_DECLARE(chain_bwd)
-template <int C, int NW, int HH>
+template <int C, int NW, int HH, bool HB>
 __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(2) void chain_bwd_kernel(ChainBwdArgs a) {
     DN_CLK_STAMP(chain_bwd, 0);
     constexpr int NT = C / 16;
@@ -133,6 +136,12 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(2) void chain_bwd_kernel(C
         // ---- hidden layers, last to first: d_a[j-1] = (d_a[j] W_j) * relu'(h_{j-1}) * dropout scale   (h > 0 <=> kept and active)
 #pragma unroll 1
         for (int j = a.n_mlp - 1; j >= 1; --j) {
+            unsigned hw[HH];      // HB: this lane's sign-bit words of h_{j-1}, bit 4 nt + e <=> h[row][16 nt + 4 q + e] > 0; requested ahead of the product
+            if constexpr (HB) {
+                const unsigned* hbp = a.hbits[j - 1];
+#pragma unroll
+                for (int hh = 0; hh < HH; ++hh) hw[hh] = hbp[(long long)rch[hh] * 4 + q];
+            }
             CH_ZERO(acc);
 #pragma unroll
             for (int T = 0; T < NK; ++T) {
@@ -141,28 +150,43 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(2) void chain_bwd_kernel(C
                 CH_PIECE_END();
             }
             const float so = ch_pow2_inv(s_act) * (j == 1 ? sw_inv[1] : (j == 2 ? sw_inv[2] : sw_inv[3]));
-            const float* hp = a.h[j - 1];
             const float ds = j == 1 ? a.dscale[0] : (j == 2 ? a.dscale[1] : a.dscale[2]);
-            float4 hv[HH][NT];
-#pragma unroll
-            for (int hh = 0; hh < HH; ++hh) {
-                const float* p = hp + (long long)rch[hh] * C + 4 * q;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) hv[hh][nt] = *reinterpret_cast<const float4*>(p + 16 * nt);   // (d_out is read again for the residual)
-            }
             float wm = 0.f;
+            if constexpr (HB) {
 #pragma unroll
-            for (int hh = 0; hh < HH; ++hh)
+                for (int hh = 0; hh < HH; ++hh) {
+                    const unsigned w = hw[hh];
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float hq[4] = {hv[hh][nt].x, hv[hh][nt].y, hv[hh][nt].z, hv[hh][nt].w};
+                    for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float t = hq[e] > 0.f ? acc[hh][nt][e] * so * ds : 0.f;
-                        acc[hh][nt][e] = t;
-                        wm = fabsf(t) > wm ? fabsf(t) : wm;
-                    }
+                        for (int e = 0; e < 4; ++e) {
+                            const float t = ((w >> (4 * nt + e)) & 1u) ? acc[hh][nt][e] * so * ds : 0.f;
+                            acc[hh][nt][e] = t;
+                            wm = fabsf(t) > wm ? fabsf(t) : wm;
+                        }
                 }
+            } else {
+                const float* hp = a.h[j - 1];
+                float4 hv[HH][NT];
+#pragma unroll
+                for (int hh = 0; hh < HH; ++hh) {
+                    const float* p = hp + (long long)rch[hh] * C + 4 * q;
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) hv[hh][nt] = *reinterpret_cast<const float4*>(p + 16 * nt);
+                }
+#pragma unroll
+                for (int hh = 0; hh < HH; ++hh)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        const float hq[4] = {hv[hh][nt].x, hv[hh][nt].y, hv[hh][nt].z, hv[hh][nt].w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float t = hq[e] > 0.f ? acc[hh][nt][e] * so * ds : 0.f;
+                            acc[hh][nt][e] = t;
+                            wm = fabsf(t) > wm ? fabsf(t) : wm;
+                        }
+                    }
+            }
             float* dj = a.d_a[j - 1];
 #pragma unroll
             for (int hh = 0; hh < HH; ++hh)
@@ -327,8 +351,8 @@ int dn_chain_bwd_pieces(int C, int with_grad, int with_rot, int n_mlp) {
     return (n_mlp - 1) * NK + (with_grad ? 3 : 2) * NK + (with_grad ? 2 * NK * (with_rot ? 2 : 1) : 0);
 }
 
-template <int C, int NW, int HH>
-static int chain_bwd_launch_nw(ChainBwdArgs a, hipStream_t stream) {
+template <int C, int NW, int HH, bool HB>
+static int chain_bwd_launch_nw_hb(ChainBwdArgs a, hipStream_t stream) {
     a.units = (a.V + 16 * HH * NW - 1) / (16 * HH * NW);
     int g = (8 / NW) * dn_num_cus();
     if (g > a.units) g = a.units;
@@ -336,10 +360,19 @@ static int chain_bwd_launch_nw(ChainBwdArgs a, hipStream_t stream) {
     const size_t smem = (size_t)DN_CH_RING * (2 * (C / 16) * 64) * sizeof(uint4);
 #ifndef DN_EMULATE
     static unsigned long long lds_opt_in = 0;   // per-device bitmap
-    { const int oe_ = dn_lds_opt_in(reinterpret_cast<const void*>(&chain_bwd_kernel<C, NW, HH>), smem, &lds_opt_in); if (oe_) return oe_; }
+    { const int oe_ = dn_lds_opt_in(reinterpret_cast<const void*>(&chain_bwd_kernel<C, NW, HH, HB>), smem, &lds_opt_in); if (oe_) return oe_; }
 #endif
-    DN_LAUNCH((chain_bwd_kernel<C, NW, HH>), dim3(g, 1, 1), dim3(64 * NW, 1, 1), smem, stream, a);
+    DN_LAUNCH((chain_bwd_kernel<C, NW, HH, HB>), dim3(g, 1, 1), dim3(64 * NW, 1, 1), smem, stream, a);
     return (int)hipGetLastError();
+}
+// the sign-bit form when every hidden layer's words are there, else the form that reads h
+static bool chain_bwd_has_bits(const ChainBwdArgs& a) {
+    for (int j = 0; j < a.n_mlp - 1; ++j) if (!a.hbits[j]) return false;
+    return a.n_mlp >= 2;
+}
+template <int C, int NW, int HH>
+static int chain_bwd_launch_nw(const ChainBwdArgs& a, hipStream_t stream) {
+    return chain_bwd_has_bits(a) ? chain_bwd_launch_nw_hb<C, NW, HH, true>(a, stream) : chain_bwd_launch_nw_hb<C, NW, HH, false>(a, stream);
 }
 template <int C>
 static int chain_bwd_launch(int npieces, const ChainBwdArgs& a_in, hipStream_t stream, int hh) {
@@ -368,12 +401,13 @@ int dn_launch_chain_bwd(int npieces, const ChainBwdArgs& a, int C, hipStream_t s
     else if (C == 64) err = chain_bwd_launch<64>(npieces, a, stream, hh);
     else err = 1;
     {
-        // algorithmic traffic: d_out read once (+ once more for the residual: L2), every saved activation read once, every gradient written once
+        // algorithmic traffic: d_out read once (+ once more for the residual: L2), every saved activation read once (the hidden ones as sign-bit words when given), every gradient written once
         const double VC = 4.0 * (double)a.V * C;
-        const double nr = 1.0 + (a.n_mlp - 1) + (a.with_grad ? 5.0 : 0.0);
+        const bool hb = chain_bwd_has_bits(a);      // h_j read as [V][4] sign-bit words (16 bytes per row) and not as [V, C] fp32
+        const double nr = 1.0 + (hb ? 0.0 : (a.n_mlp - 1)) + (a.with_grad ? 5.0 : 0.0);
         const double nw = (a.n_mlp - 1) + 2.0 + (a.with_grad ? 3.0 : 0.0);
         const double prod = (a.n_mlp - 1) + (a.with_grad ? 3.0 : 2.0) + (a.with_grad ? (a.with_rot ? 4.0 : 2.0) : 0.0);
-        dn_prof_end(DN_K_CHAIN_BWD, stream, 2.0 * (double)a.V * C * C * prod, VC * (nr + nw));
+        dn_prof_end(DN_K_CHAIN_BWD, stream, 2.0 * (double)a.V * C * C * prod, VC * (nr + nw) + (hb ? 16.0 * (double)a.V * (a.n_mlp - 1) : 0.0));
     }
     return err;
 }

@@ -513,12 +513,16 @@ struct ChainArgs {
     const float* wa_amax;                 // magnitude word of A_re / A_im (joint)
     const float* w_amax[DN_CH_LAYERS];    // of W_j
     const float* bias[DN_CH_LAYERS];
-    const uint8_t* mask[DN_CH_LAYERS];    // explicit keep-mask applied to the OUTPUT of layer j ([V, C] bytes), or null
-    unsigned long long seed[DN_CH_LAYERS];   // != 0 with mask == null: keep bits drawn in the epilogue (dn_keep_bits)
+    // (per HIDDEN layer j < n_mlp - 1 <= DN_CH_LAYERS - 1: mask, seed, h, hbits.  The last layer has none of them, so these arrays hold
+    // DN_CH_LAYERS - 1 entries: with hbits added the kernel-argument block stays at the size it had with three DN_CH_LAYERS-sized arrays,
+    // and the kernels keep no more argument words live in SGPRs than before)
+    const uint8_t* mask[DN_CH_LAYERS - 1];   // explicit keep-mask applied to the OUTPUT of layer j ([V, C] bytes), or null
+    unsigned long long seed[DN_CH_LAYERS - 1];   // != 0 with mask == null: keep bits drawn in the epilogue (dn_keep_bits)
     const unsigned long long* seed_dev;
     // outputs (null: not saved)
     float* gx; float* gy; float* g; float* bre; float* bim;
-    float* h[DN_CH_LAYERS];
+    float* h[DN_CH_LAYERS - 1];
+    unsigned* hbits[DN_CH_LAYERS - 1];    // optional (C <= 128): the sign bits of h_j, [V][4] words: bit 4 nt + e of word (row, q) <=> h_j[row][16 nt + 4 q + e] > 0
     float* out;
     // magnitudes
     const float* x_amax; const float* xd_amax; const float* grad_norm;
@@ -542,6 +546,7 @@ struct ChainArgs {
 struct ChainBwdArgs {
     const float* d_out;                   // [V, C] gradient of the block output
     const float* h[DN_CH_LAYERS];         // saved post-ReLU(+dropout) hidden activations h_j, j < n_mlp - 1
+    const unsigned* hbits[DN_CH_LAYERS];  // their sign bits as words (ChainArgs.hbits); all layers j < n_mlp - 1 set: the kernel reads these and not h
     const float* g; const float* gx; const float* gy; const float* bre; const float* bim;   // saved gradient-feature tensors (with_grad)
     int V;
     int with_grad, with_rot, n_mlp;
@@ -565,6 +570,7 @@ size_t dn_chain_ws_bytes(int C, int with_grad, int with_rot, int n_mlp);
 bool dn_chain_eligible(int C, int n_mlp, const int* widths, int with_grad, long long g_nnz, int V, int backward = 0);   // (the backward kernel exists at C = 64, 128)
 int dn_launch_chain_prep(const ChainPrepArgs& pa, int npieces, int C, hipStream_t stream);
 int dn_launch_chain_fwd(int npieces, const ChainArgs& a, int C, hipStream_t stream, int hh = 2);
+bool dn_chain_fwd_writes_hbits(int C, int hh);      // whether that launch writes ChainArgs.hbits (false: the caller packs them from the stored h, dn_launch_hbits_pack)
 // ---- spectral-gradient operands (dn_spectral.hip): the gradient apply re-associated, gx = G_X (Phi ys) = (G_X Phi) ys.  Built once per
 // mesh batch: G_X Phi, G_Y Phi by a CSR gather accumulated in fp64, then [Phi | G_X Phi | G_Y Phi] split into fp16 (hi, lo) planes in the
 // operand-fragment order of the chained forward kernel, 16 rows per group, every mesh padded to whole 64-row units.
@@ -702,6 +708,8 @@ struct HeadArgs {
 int dn_launch_head_fwd(const HeadArgs& a, int nb, float* loss, float* count, hipStream_t stream);
 int dn_launch_head_bwd(const HeadArgs& a, hipStream_t stream);
 int dn_launch_dtanh(const float* dg, const float* g, float* out, long long n, hipStream_t stream);
+// sign-bit words of a stored hidden activation h [V, C], C = 64 or 128 (dn_block_saved_t.hbits): bits[row][q] bit 4 nt + e <=> h[row][16 nt + 4 q + e] > 0
+int dn_launch_hbits_pack(const float* h, unsigned* bits, int V, int C, hipStream_t stream);
 int dn_launch_reduce_pair(const float* pa, float* oa, long long la, const float* pb, float* ob, long long lb, int n, hipStream_t stream);
 int dn_launch_hks(const float* evals, const float* evecs, const float* scales, int B, int V, int K, int S, long long scale_stride,
                   float* out, hipStream_t stream);

@@ -533,6 +533,33 @@ int dn_launch_dtanh(const float* dg, const float* g, float* out, long long n, hi
     return (int)hipGetLastError();
 }
 
+// Sign-bit words of a stored hidden activation (dn_block_saved_t.hbits) for the forward routes that do not run the chained row kernel, which
+// forms them in its epilogue: one thread per word, bit 4 nt + e of word (row, q) <=> h[row][16 nt + 4 q + e] > 0.
+template <int C>
+__global__ __launch_bounds__(256) void hbits_pack_kernel(const float* h, unsigned* bits, long long nwords) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nwords; i += (long long)gridDim.x * 256) {
+        const float* p = h + (i >> 2) * C + 4 * (i & 3);
+        unsigned w = 0u;
+#pragma unroll
+        for (int nt = 0; nt < C / 16; ++nt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w |= (p[16 * nt + e] > 0.f ? 1u : 0u) << (4 * nt + e);
+        bits[i] = w;
+    }
+}
+int dn_launch_hbits_pack(const float* h, unsigned* bits, int V, int C, hipStream_t stream) {
+    if (V <= 0) return 0;
+    if (!h || !bits || (C != 64 && C != 128)) return 1;
+    const long long nwords = 4ll * V;
+    long long nb = (nwords + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    dn_prof_begin(DN_K_SMALL, stream);
+    if (C == 128) DN_LAUNCH(hbits_pack_kernel<128>, dim3((unsigned)nb, 1, 1), dim3(256, 1, 1), 0, stream, h, bits, nwords);
+    else DN_LAUNCH(hbits_pack_kernel<64>, dim3((unsigned)nb, 1, 1), dim3(256, 1, 1), 0, stream, h, bits, nwords);
+    dn_prof_end(DN_K_SMALL, stream, 0.0, 4.0 * (double)V * C + 16.0 * (double)V);
+    return (int)hipGetLastError();
+}
+
 // ---- thin products with a tiny contraction / output width (first_lin: C_in = 3 or 16; last_lin backward) ----
 // A thread owns 4 output columns for all the rows it visits and keeps their K <= 16 weights in registers; per row it
 // reads the K inputs (wave-broadcast) and writes one float4.  Bandwidth-bound on the output stream.

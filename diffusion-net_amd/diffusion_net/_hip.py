@@ -53,7 +53,7 @@ class BlockParamsStruct(C.Structure):
 class BlockSavedStruct(C.Structure):
     _fields_ = [
         ("xs", _vp), ("xd", _vp), ("gx", _vp), ("gy", _vp), ("g", _vp), ("bre", _vp), ("bim", _vp),
-        ("h", _vp * MAX_MLP), ("amax", _vp),
+        ("h", _vp * MAX_MLP), ("amax", _vp), ("hbits", _vp * MAX_MLP),
     ]
 
 

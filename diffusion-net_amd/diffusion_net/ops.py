@@ -402,14 +402,15 @@ class BlockSaved(NamedTuple):
     words: torch.Tensor      # [magnitude words of the saved activations | max |out|]
     feats: list              # gx, gy, g, bre, bim with gradient features, else empty
     hs: list                 # post-ReLU hidden activations of the MiniMLP
+    hbits: torch.Tensor = None   # int32 [n_mlp - 1, V, 4] at C = 64, 128 (else [0, V, 4]: no words exist): their signs as bit words (dn_block_saved_t.hbits); None: not passed
 
     def flat(self):
-        return [self.xs, self.xd, self.words, *self.feats, *self.hs]
+        return [self.xs, self.xd, self.words, self.hbits, *self.feats, *self.hs]
 
     @classmethod
     def from_flat(cls, cfg, ts):
         n_feat = 5 if cfg.with_grad else 0
-        return cls(ts[0], ts[1], ts[2], list(ts[3:3 + n_feat]), list(ts[3 + n_feat:]))
+        return cls(ts[0], ts[1], ts[2], list(ts[4:4 + n_feat]), list(ts[4 + n_feat:]), ts[3])
 
     def struct(self):
         sv = _hip.BlockSavedStruct()
@@ -419,10 +420,14 @@ class BlockSaved(NamedTuple):
         for i, h in enumerate(self.hs):
             sv.h[i] = h.data_ptr()
         sv.amax = self.words.data_ptr()
+        if self.hbits is not None:
+            base, step = self.hbits.data_ptr(), 4 * self.hbits.stride(0)      # (no per-layer tensor view: this runs once per block call on the host)
+            for i in range(self.hbits.shape[0]):
+                sv.hbits[i] = base + i * step
         return sv
 
     def named(self):
-        return {"xs": self.xs, "xd": self.xd, **dict(zip(("gx", "gy", "g", "bre", "bim"), self.feats)), "h": list(self.hs), "words": self.words}
+        return {"xs": self.xs, "xd": self.xd, **dict(zip(("gx", "gy", "g", "bre", "bim"), self.feats)), "h": list(self.hs), "words": self.words, "hbits": self.hbits}
 
 
 def block_fwd(mb, cfg, masks, x, time, A_re, A_im, Ws, bs, x_amax=None, save=True, clamp=False):
@@ -444,7 +449,8 @@ def block_fwd(mb, cfg, masks, x, time, A_re, A_im, Ws, bs, x_amax=None, save=Tru
     saved = sv = None
     if save:
         saved = BlockSaved(new(mb.n_mesh, mb.k_eig, Cc), new(V, Cc), words, [new(V, Cc) for _ in range(5)] if cfg.with_grad else [],
-                           [new(V, cfg.widths[i + 1]) for i in range(cfg.n_mlp - 1)])
+                           [new(V, cfg.widths[i + 1]) for i in range(cfg.n_mlp - 1)],
+                           torch.empty(cfg.n_mlp - 1 if Cc in (64, 128) else 0, V, 4, dtype=torch.int32, device=x.device))
         sv = saved.struct()
     ws, n = _ws(mb, L.dn_block_fwd_workspace_bytes(mb.ref(), C.byref(p), int(save)))
     _hip.check(L.dn_block_fwd_f32(mb.ref(), C.byref(p), x.data_ptr(), out.data_ptr(), C.byref(sv) if save else None, ws.data_ptr(), n,

@@ -113,7 +113,7 @@ def _masks(seed: int, seed_dev: Optional[Tensor]):
 @_op("diffusion_net::block")
 def block(x: Tensor, time: Tensor, A_re: Optional[Tensor], A_im: Optional[Tensor], wb: List[Tensor], mb: int, cfg: int, seed: int,
           seed_dev: Optional[Tensor], n_mesh: int, k_eig: int) -> List[Tensor]:
-    """-> [out, xs, xd, words, (gx, gy, g, bre, bim), h_0 ...]: the output and what the backward needs besides the inputs."""
+    """-> [out, xs, xd, words, hbits, (gx, gy, g, bre, bim), h_0 ...]: the output and what the backward needs besides the inputs."""
     # save on: this op always returns what its backward op needs; clamp off: `time` is an input of a custom op that declares no mutation,
     # the caller has clamped it (layers.forward_packed)
     x = _in(x, _obj(mb))
@@ -127,7 +127,8 @@ def _(x, time, A_re, A_im, wb, mb, cfg, seed, seed_dev, n_mesh, k_eig):
     # (shapes from the operands alone: the handles may be symbolic while tracing)
     V, Cw = x.shape[0], x.shape[1]
     new = lambda *s: x.new_empty(*s)
-    outs = [new(V, Cw), new(n_mesh, k_eig, Cw), new(V, Cw), new(_hip.BLOCK_AMAX_WORDS + 1)]
+    outs = [new(V, Cw), new(n_mesh, k_eig, Cw), new(V, Cw), new(_hip.BLOCK_AMAX_WORDS + 1),
+            x.new_empty(len(wb) // 2 - 1 if Cw in (64, 128) else 0, V, 4, dtype=torch.int32)]
     outs += [new(V, Cw) for _ in range(5 if A_re is not None else 0)]
     outs += [new(V, w.shape[0]) for w in wb[0:-2:2]]
     return outs

@@ -123,6 +123,14 @@ typedef struct dn_block_saved {
     float* h[DN_MAX_MLP_LAYERS];       /* h[i], i < n_mlp-1: [v_total, widths[i+1]] post-ReLU(+dropout) */
     float* amax;                       /* optional [DN_BLOCK_AMAX_WORDS] device floats: magnitudes of the saved activations (written by the
                                           forward, read by the backward).  NULL: both calls use the split-bf16 engine throughout. */
+    /* Optional (round 7): the signs of the hidden activations as bit words, one array per hidden layer i < n_mlp-1 whose width is C, for
+     * C = 64 and C = 128 (no words exist at other widths: the field is ignored there).  hbits[i]: [v_total][4] uint32, 16 bytes per row; the word
+     * at (row, q) has bit 4 nt + e set iff h[i][row][16 nt + 4 q + e] > 0 (C = 128: all 32 bits, C = 64: the low 16; the other bits are zero).
+     * A non-NULL hbits[i] is WRITTEN by dn_block_fwd_f32 on every route (by the chained row kernel from the values it stores, else by one small
+     * pass over the stored h[i]) and READ by dn_block_bwd_f32 whenever its chained row kernel runs, which then does not read h[i] (the
+     * weight-gradient products still do: h stays in the saved set).  All of hbits[i], i < n_mlp-1, or none: NULL = the behaviour of version 600
+     * in both directions.  Results are bit-identical either way (the same predicate on the same fp32 value). */
+    uint32_t* hbits[DN_MAX_MLP_LAYERS];
 } dn_block_saved_t;
 #define DN_BLOCK_AMAX_WORDS 16
 
@@ -136,7 +144,7 @@ typedef struct dn_block_grads {
     float* d_x_amax;                   /* optional: device float that receives max |d_x| */
 } dn_block_grads_t;
 
-int dn_version(void);         /* 600: round-6 layout (dn_mesh_batch_t.sg_pack ...); 500: round 5 (dn_mesh_batch_t.df_plan ..., dn_set_option) */
+int dn_version(void);         /* 700: dn_block_saved_t.hbits; 600: round-6 layout (dn_mesh_batch_t.sg_pack ...); 500: round 5 (dn_mesh_batch_t.df_plan ..., dn_set_option) */
 int dn_tile_rows(void);      /* rows per entry of dn_mesh_batch_t.tiles (128) */
 int dn_tn_target_chunks(void);  /* how many entries dn_mesh_batch_t.chunks should have on the current device for the split-V products to fill it in
                                    whole rounds: one workgroup slot per CU (wave-specialised kernel).  Any chunk list is CORRECT; this one is fastest. */

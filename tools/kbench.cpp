@@ -4,6 +4,7 @@
 //   tools/kbench [--lib path.so] [--meshes 16] [--verts 10000] [--C 128] [--K 128] [--reps 20] [--ops a,b,..] [--check]
 // Ops: to_basis from_basis diffusion diffusion_bwd spmm gradfeat gradfeat_bwd linear linear_relu linear_bwd
 //      block_inf block_fwd block_bwd copy copyk (hand-written float4 copy / read / fill kernels on 2 GiB of rotating buffers)
+// Environment: KB_NO_HBITS=1 leaves dn_block_saved_t.hbits NULL (block_fwd writes no sign-bit words, block_bwd's chained kernel reads h: A/B of its two forms).
 // Every op line: avg us (hipEvents around `reps` back-to-back calls), algorithmic GB/s and, with --check, the worst error of a
 // row sample against an fp64 host evaluation of the same formula (relative to the largest reference magnitude).
 #include <hip/hip_runtime.h>
@@ -206,6 +207,9 @@ int main(int argc, char** argv) {
     sv.xs = devz((size_t)n_mesh * K * C); sv.xd = devz((size_t)V * C); sv.gx = devz((size_t)V * C); sv.gy = devz((size_t)V * C); sv.g = devz((size_t)V * C);
     sv.bre = devz((size_t)V * C); sv.bim = devz((size_t)V * C); sv.h[0] = devz((size_t)V * C); sv.h[1] = devz((size_t)V * C);
     sv.amax = devz(DN_BLOCK_AMAX_WORDS);
+    // sign-bit words of the hidden activations ([V][4] uint32 per layer; C = 64, 128): block_fwd writes them, block_bwd's chained kernel reads them and
+    // not h.  KB_NO_HBITS=1: the saved set without them (A/B of the two forms of the chained backward with one library)
+    if (!getenv("KB_NO_HBITS")) for (int j = 0; j < 2; ++j) sv.hbits[j] = reinterpret_cast<uint32_t*>(devz((size_t)V * 4));
     {   // block input / incoming gradient magnitudes (x = hx, d_out = hy), as the previous / next block would hand them over
         float ax = 0.f, ay = 0.f;
         for (float v : hx) ax = std::max(ax, fabsf(v));
