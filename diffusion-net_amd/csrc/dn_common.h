@@ -713,6 +713,9 @@ int dn_launch_hbits_pack(const float* h, unsigned* bits, int V, int C, hipStream
 int dn_launch_reduce_pair(const float* pa, float* oa, long long la, const float* pb, float* ob, long long lb, int n, hipStream_t stream);
 int dn_launch_hks(const float* evals, const float* evecs, const float* scales, int B, int V, int K, int S, long long scale_stride,
                   float* out, hipStream_t stream);
+// exact k-nearest-neighbour search (dn_knn.hip): n_split target slices of tiles_per_slice 64-target tiles each; pk / pi [n_split][k][n_src] when n_split > 1
+int dn_launch_knn(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int largest, int omit_diagonal, int n_split,
+                  int tiles_per_slice, float* dist, long long* idx, float* pk, int* pi, hipStream_t stream);
 // COO -> CSR + CSR of the transpose (dn_pack.hip).  rows == nullptr: entry j belongs to row j / row_div (gather patterns)
 size_t dn_pack_ws_bytes(long long nnz, int n_cols);
 int dn_launch_coo_to_csr(const long long* rows, int row_div, const long long* cols, const float* vx, const float* vy, long long nnz, int n_rows,

@@ -7,3 +7,4 @@ the HIP library; the first hot-path op does, and raises if either is missing."""
 from . import utils, geometry, layers, synthetic, batch, ops, graphs, autograph  # noqa: F401
 from .batch import MeshBatch, GatherPattern  # noqa: F401
 from .layers import DiffusionNet  # noqa: F401
+from .geometry import find_knn  # noqa: F401

@@ -15,6 +15,7 @@ import torch
 MAX_MLP = 8
 BLOCK_AMAX_WORDS = 16       # include/diffnet_hip.h: DN_BLOCK_AMAX_WORDS
 HEAD_MAX_CLASSES = 2048   # dn_head.hip: 64 lanes x DN_HEAD_CPL classes per row
+KNN_MAX_K = 32            # include/diffnet_hip.h: DN_KNN_MAX_K
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # DN_LIB_VARIANT=<tag> selects libdiffnet_hip_<tag>.so (same sources, other build flags) for A/B experiments
 _VARIANT = os.environ.get("DN_LIB_VARIANT", "")
@@ -110,6 +111,9 @@ _SIGNATURES = {
     "dn_head_fwd_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "dn_head_bwd_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "dn_hks_f32": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "dn_knn_max_k": (C.c_int, []),
+    "dn_knn_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "dn_knn_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
     "dn_coo_to_csr_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "dn_coo_to_csr_i64": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int] + [_vp] * 7 + [_vp, C.c_size_t, _vp]),
     "dn_checksum128": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp, _vp]),

@@ -4,8 +4,10 @@ Signatures follow the reference (geometry.py:572-598): batched tensors, basis [B
 values [B,V,C] / [B,K,C], massvec [B,V] (an unbatched leading dimension is accepted too).
 The host-side operator precompute keeps the reference's names here (``compute_operators``, ``get_operators``,
 ``get_all_operators``, ``normalize_positions``, ``compute_hks[_autoscale]``) and lives in ``precompute.py``
-(numpy/scipy restatement, triangle meshes).
+(numpy/scipy restatement, triangle meshes).  ``find_knn`` is the nearest-neighbour query of the evaluation scripts.
 """
+from collections import namedtuple
+
 import torch
 
 from . import ops
@@ -55,3 +57,79 @@ def compute_hks(evals, evecs, scales):
 def compute_hks_autoscale(evals, evecs, count):
     scales = torch.logspace(-2, 0.0, steps=count, device=evals.device, dtype=evals.dtype)   # geometry.py:630-633
     return compute_hks(evals, evecs, scales)
+
+
+KnnResult = namedtuple("KnnResult", ["values", "indices"])
+_KNN_CHUNK_PAIRS = 1 << 26     # pairs per distance block of the torch path ...
+_KNN_CHUNK_ELEMS = 1 << 27     # ... and elements of its N x M x D difference block
+
+
+def _knn_torch(source, target, k, largest, omit_diagonal):
+    """Row blocks of the reference's own formula -- norm of the expanded difference -- and ``topk`` of each: differentiable, any dtype, any
+    k <= M, bounded memory (at most 2^26 pairs and 2^27 difference elements at a time).  Not ``torch.cdist``: past some ten million pairs
+    per call its non-matmul mode returned wrong distances on the device (measured at both workload shapes, tools/knn_timing.py), and its
+    matmul mode is the |a|^2 + |b|^2 - 2ab expansion, whose cancellation reorders near neighbours."""
+    N, M, D = source.shape[0], target.shape[0], source.shape[1]
+    rows = max(1, min(N, _KNN_CHUNK_PAIRS // max(M, 1), _KNN_CHUNK_ELEMS // max(M * D, 1)))
+    masked = float("-inf") if largest else float("inf")
+    vals, inds = [], []
+    for r0 in range(0, N, rows):
+        d = (source[r0:r0 + rows, None, :] - target[None, :, :]).norm(dim=-1)
+        if omit_diagonal:
+            own = torch.arange(r0, r0 + d.shape[0], device=d.device)[:, None] == torch.arange(M, device=d.device)[None, :]
+            d = d.masked_fill(own, masked)
+        top = torch.topk(d, k=k, largest=largest, sorted=True)
+        vals.append(top.values)
+        inds.append(top.indices)
+    if not vals:
+        return KnnResult(source.new_empty(0, k), torch.empty(0, k, dtype=torch.int64, device=source.device))
+    return KnnResult(torch.cat(vals), torch.cat(inds))
+
+
+def _knn_kdtree(source, target, k, omit_diagonal):
+    """Host route of ``method='cpu_kd'``: an sklearn KD-tree over the targets, distances recomputed in torch from the indices."""
+    import numpy as np
+    from sklearn.neighbors import KDTree    # only this route needs sklearn: the package does not import it otherwise
+    from .utils import toNP
+    tree = KDTree(toNP(target))
+    nbr = tree.query(toNP(source), k=k + 1 if omit_diagonal else k, return_distance=False)
+    if omit_diagonal:
+        # Drop the point itself from its row; a row where duplicates pushed it out of the k + 1 hits loses its last hit instead.
+        keep = nbr != np.arange(nbr.shape[0])[:, None]
+        keep[keep.all(axis=1), -1] = False
+        nbr = nbr[keep].reshape(nbr.shape[0], k)
+    inds = torch.as_tensor(nbr, dtype=torch.int64, device=source.device)
+    return KnnResult((source[:, None, :] - target[inds]).norm(dim=-1), inds)
+
+
+def find_knn(points_source, points_target, k, largest=False, omit_diagonal=False, method="brute"):
+    """The k nearest neighbours of every source point among the target points (geometry.py:667-724): ``(values, indices)``, sorted in
+    increasing distance (``largest``: the k farthest, decreasing).  The result unpacks as a pair and has ``.values`` / ``.indices``.
+
+    fp32 tensors on a ROCm device with nothing requiring grad and k <= 32 run the exact HIP search (``ops.knn``) for ``'brute'`` AND
+    ``'cpu_kd'`` -- both are exact searches, so the evaluation scripts' ``method='cpu_kd'`` never leaves the device, and there is no size
+    switch.  Other device tensors take a row-chunked torch path (the reference's difference formula; differentiable, as its ``'brute'`` branch); host tensors do what
+    the reference does (``'brute'``: torch, ``'cpu_kd'``: ``sklearn.neighbors.KDTree``).
+    Difference from the reference: with duplicate points and ``omit_diagonal`` its KD-tree branch may drop a duplicate other than the point
+    itself; the device routes always exclude index i.  The distances are identical."""
+    if omit_diagonal and points_source.shape[0] != points_target.shape[0]:
+        raise ValueError("omit_diagonal can only be used when source and target are same shape")
+    if method not in ("brute", "cpu_kd"):
+        raise ValueError("unrecognized method")
+    if method == "cpu_kd" and largest:
+        raise ValueError("can't do largest with cpu_kd")
+    if points_source.device != points_target.device:
+        raise RuntimeError("find_knn: source points on %s, target points on %s" % (points_source.device, points_target.device))
+    k = int(k)
+    if points_source.is_cuda:
+        hip = (points_source.dtype == torch.float32 and points_target.dtype == torch.float32 and 1 <= k <= ops._hip.KNN_MAX_K
+               and not points_source.requires_grad and not points_target.requires_grad)
+        if not hip:
+            return _knn_torch(points_source, points_target, k, largest, omit_diagonal)
+        if torch.compiler.is_compiling():
+            from . import torchlib  # noqa: F401  (registers torch.ops.diffusion_net.knn)
+            return KnnResult(*torch.ops.diffusion_net.knn(points_source, points_target, k, bool(largest), bool(omit_diagonal)))
+        return KnnResult(*ops.knn(points_source, points_target, k, largest, omit_diagonal))
+    if method == "cpu_kd":
+        return _knn_kdtree(points_source, points_target, k, omit_diagonal)
+    return _knn_torch(points_source, points_target, k, largest, omit_diagonal)

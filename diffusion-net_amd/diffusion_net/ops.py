@@ -219,6 +219,43 @@ def hks(evals, evecs, scales):
     return out[0] if squeeze else out
 
 
+@_on_device
+def _knn_launch(src, tgt, k, largest, omit_diagonal, n_split):
+    L = _hip.lib()
+    N, D = src.shape
+    M = tgt.shape[0]
+    dist = torch.empty(N, k, dtype=torch.float32, device=src.device)
+    idx = torch.empty(N, k, dtype=torch.int64, device=src.device)
+    nbytes = L.dn_knn_workspace_bytes(N, M, D, k, n_split)
+    ws = _hip.workspace(src.device, nbytes) if nbytes else None
+    _hip.check(L.dn_knn_f32(src.data_ptr(), N, tgt.data_ptr(), M, D, k, int(largest), int(omit_diagonal), n_split, dist.data_ptr(),
+                            idx.data_ptr(), _hip.ptr(ws), ws.numel() if ws is not None else 0, _hip.stream_of(src)), "dn_knn_f32")
+    return dist, idx
+
+
+def knn(src, tgt, k, largest=False, omit_diagonal=False, n_split=0):
+    """Exact k nearest (``largest``: farthest) rows of ``tgt`` [M, D] for every row of ``src`` [N, D] -> (dist [N, k] fp32, idx [N, k] int64),
+    sorted by distance, equal distances by the lower target index (geometry.py:667-724), forward only.  ``omit_diagonal``: target i is no
+    candidate of row i.  ``n_split``: how many target slices are searched in parallel (0: the library chooses); the result does not depend on it."""
+    _hip.require_device(src)
+    _hip.require_device(tgt)
+    src, tgt = _f32c(src), _f32c(tgt)
+    if src.dim() != 2 or tgt.dim() != 2 or src.shape[1] != tgt.shape[1] or src.shape[1] < 1:
+        raise ValueError("knn takes [N, D] and [M, D] points (got %s and %s)" % (tuple(src.shape), tuple(tgt.shape)))
+    if src.device != tgt.device:
+        raise RuntimeError("knn: source points on %s, target points on %s" % (src.device, tgt.device))
+    k, n_split = int(k), int(n_split)
+    if omit_diagonal and src.shape[0] != tgt.shape[0]:
+        raise ValueError("omit_diagonal can only be used when source and target are same shape")
+    if not 1 <= k <= _hip.KNN_MAX_K:
+        raise ValueError("knn kernel takes 1 <= k <= %d (got %d)" % (_hip.KNN_MAX_K, k))
+    if k > tgt.shape[0] - int(bool(omit_diagonal)):
+        raise ValueError("k = %d neighbours asked of %d candidates" % (k, tgt.shape[0] - int(bool(omit_diagonal))))
+    if n_split < 0:
+        raise ValueError("n_split must be >= 0")
+    return _knn_launch(src, tgt, k, bool(largest), bool(omit_diagonal), n_split)
+
+
 # ----------------------------------------------------------------------------------------------
 # gradient sinks: a parameter may carry ``_dn_grad_sink`` (set by dist.FlatParams: its slice of the flat
 # gradient bucket).  Backward then ACCUMULATES the parameter gradients of a whole op into their sinks with

@@ -19,7 +19,7 @@ run (a dead handle raises a RuntimeError that says so).  Handles are graph const
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -286,3 +286,14 @@ def _head_backward(ctx, grads):
 
 
 head.register_autograd(_head_backward, setup_context=_head_setup)
+
+
+# ------------------------------------------------------------------------------------------------ nearest neighbours (forward only)
+@_op("diffusion_net::knn")
+def knn(src: Tensor, tgt: Tensor, k: int, largest: bool, omit_diagonal: bool) -> Tuple[Tensor, Tensor]:
+    return ops.knn(src, tgt, k, largest, omit_diagonal)
+
+
+@knn.register_fake
+def _(src, tgt, k, largest, omit_diagonal):
+    return src.new_empty(src.shape[0], k, dtype=torch.float32), src.new_empty(src.shape[0], k, dtype=torch.int64)   # ops.knn is fp32

@@ -328,6 +328,22 @@ int dn_head_bwd_f32(const float* logp, int n_out, int C, const int32_t* t_rowptr
 int dn_hks_f32(const float* evals, const float* evecs, const float* scales, int B, int V, int K, int S, int scales_per_batch,
                float* out, void* stream);
 
+/* ---- geometry.find_knn (geometry.py:667-724): exact brute-force k-nearest-neighbour search that never forms the N x M matrix (dn_knn.hip).
+ *      src [n_src, dim], tgt [n_tgt, dim] fp32 row-major; dist [n_src, k] fp32, idx [n_src, k] int64.  Row i holds the k targets with the
+ *      smallest Euclidean distance to src[i] in increasing order (largest: the k largest, decreasing); omit_diagonal: target i is no
+ *      candidate of row i (needs n_src == n_tgt).  Distances are the reference's difference form (fp32 chain of (a_d - b_d)^2 over d, one
+ *      sqrtf); the order key is that squared distance and equal keys go to the lower target index, for `largest` as well.  The result is
+ *      bit-identical from run to run and for every n_split.  Inputs are assumed finite.
+ *      n_split: 0 = the library chooses how many contiguous target slices to search in parallel; >= 1 = that many (clamped to the
+ *      number of 64-target tiles).  More than one slice needs the workspace (partial lists, merged by a second kernel).
+ *      Returns 0 on success (n_src == 0: nothing is launched) and non-zero WITHOUT launching for k < 1, k > DN_KNN_MAX_K,
+ *      k > n_tgt - (omit_diagonal ? 1 : 0), dim < 1, omit_diagonal with n_src != n_tgt, or a workspace smaller than the query says. */
+#define DN_KNN_MAX_K 32
+int dn_knn_max_k(void);
+size_t dn_knn_workspace_bytes(int n_src, int n_tgt, int dim, int k, int n_split);
+int dn_knn_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int largest, int omit_diagonal, int n_split,
+               float* dist, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
