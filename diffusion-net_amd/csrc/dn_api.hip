@@ -21,11 +21,11 @@ static_assert(sizeof(dn_tile_t) == sizeof(DnTile), "tile layout");
 enum { F16_TOB = 1, F16_FROMB = 2, F16_GF = 4, F16_MLP = 8, F16_LBI = 16, F16_GFB = 32, F16_TOB_B = 64, F16_FROMB_B = 128 };
 namespace {
 struct Opt { const char* name; std::atomic<int> value; };
-enum { O_CHAIN, O_CHAIN_MIN_ROWS, O_CHAIN_SMALL_ROWS, O_CHAIN_NW, O_CHAIN_HH, O_F16, O_F16_MASK, O_F16_WGRAD, O_DIFFUSE, O_DIFFUSE_GROUPS, O_DIFFUSE_ORDER, O_DIFFUSE_FLAGS, O_DIFFUSE_SPLIT, O_SPECTRAL_GRAD, O_COUNT };
+enum { O_CHAIN, O_CHAIN_MIN_ROWS, O_CHAIN_SMALL_ROWS, O_CHAIN_NW, O_CHAIN_HH, O_F16, O_F16_MASK, O_F16_WGRAD, O_DIFFUSE, O_SPECTRAL_GRAD, O_COUNT };
 Opt g_opt[O_COUNT] = {
     {"chain", 1}, {"chain_min_rows", 0}, {"chain_small_rows", 0}, {"chain_nw", 0}, {"chain_hh", 0}, {"f16", 1},
     {"f16_mask", F16_GF | F16_MLP | F16_LBI | F16_GFB | F16_FROMB_B}, {"f16_wgrad", 0},
-    {"diffuse", 2}, {"diffuse_groups", 1}, {"diffuse_order", 0}, {"diffuse_flags", DN_DF_FLAG_DEFER}, {"diffuse_split", 0}, {"spectral_grad", 1},
+    {"diffuse", 2}, {"spectral_grad", 1},
 };
 inline int opt(int i) { return g_opt[i].value.load(std::memory_order_relaxed); }
 }  // namespace
@@ -104,15 +104,14 @@ void tn_finish(TnArgs& g) {
 }
 
 // ---- dn_diffuse.hip, for batches that carry a plan, K = C = 128, 16-byte aligned operands.  Option "diffuse":
-//   2 (default)  the back-projection of every diffusion (and of dn_from_basis_f32) is the DIRECT row product launch (DiffuseRoute.direct)
-//   1            the whole operator as one persistent launch (DiffuseRoute.one): correct on any residency, measured slower than the launches on
-//                every batch but many-small-meshes ones -- kept selectable
-//   0            the wave-specialised row GEMM of rounds 1-4
+//   non-zero (default 2)  the back-projection of every diffusion (and of dn_from_basis_f32) is the DIRECT row product launch (DiffuseRoute.direct)
+//   0                     the wave-specialised row GEMM of rounds 1-4
+// (the round-5 one-launch form of the whole operator, once value 1, is archived under tools/experiments/diffusion_one_launch/)
 // DiffuseRoute: how a diffusion (forward, backward, or a back-projection alone) at width C runs on this batch.  Computed ONCE per call from the
 // batch and the options; the size query, the layout and the body read that one value.  What depends on the call's pointers (alignment, operands
 // the caller left out) refines it in the call.
 struct DiffuseRoute {
-    bool one, direct;
+    bool direct;
     bool wide;      // the forward back-projection at K = C = 256 as the ring kernel of dn_backproject_wide.hip (3-term engine; option "diffuse" != 0;
                     // needs a workspace for the split spectrum: the block calls and dn_diffusion_f32 pass one, callers without take the row GEMM)
 };
@@ -122,22 +121,9 @@ DiffuseRoute diffuse_route(const dn_mesh_batch_t* mb, int C) {
     // dn_mesh_batch_t.df_v_total, set by whoever called dn_diffusion_plan() -- for this batch's row count; anything else takes the row GEMM)
     const bool plan = mb->df_plan && mb->df_n_wg > 0 && mb->k_eig == 128 && C == 128 && mb->df_n_wg == dn_num_cus() && mb->df_v_total == mb->v_total;
     DiffuseRoute r;
-    r.one = o == 1 && plan && mb->df_n_groups > 0 && mb->df_n_groups <= DN_DF_MAX_GROUPS;
     r.direct = o != 0 && plan && mb->df_n_groups == 1;
     r.wide = o != 0 && mb->tiles && dn_backproject_wide_ok(mb->k_eig, C, mb->n_tiles) && al16(mb->evecs);
     return r;
-}
-int diffuse_dt_rows(const dn_mesh_batch_t* mb) { return dn_diffuse_dt_rows(mb->df_n_wg, mb->df_n_groups); }
-DfLaunch diffuse_new(const dn_mesh_batch_t* mb, void* ws) {
-    DfLaunch L;
-    memset(&L, 0, sizeof(L));
-    L.plan = T(mb->df_plan); L.n_wg = mb->df_n_wg; L.n_groups = mb->df_n_groups; L.n_mesh = mb->n_mesh;
-    L.evecs = mb->evecs; L.mass = mb->mass; L.evals = mb->evals; L.ws = ws;
-    L.order = opt(O_DIFFUSE_ORDER); L.flags = opt(O_DIFFUSE_FLAGS); L.split = opt(O_DIFFUSE_SPLIT); L.acct_rows = mb->v_total;
-    return L;
-}
-bool diffuse_aligned(const void* a, const void* b, const void* c, const void* d, const void* e, const void* f) {
-    return al16(a) && al16(b) && al16(c) && al16(d) && al16(e) && al16(f);
 }
 
 // ---- building blocks shared by the per-op and the fused-block entry points ----
@@ -323,30 +309,20 @@ bool block_params_ok(const dn_block_params_t* p) {
 // ---- the diffusion operator (layers.py:210) and its backward: one stage each, called by dn_diffusion_*_f32 and by the block calls
 struct DiffuseWs {
     float *partial, *spec, *dtp;      // split-V partials [n_chunks, K, C]; the scaled spectrum (backward: its gradient) [n_mesh, K, C]; d_t rows (backward)
-    float *one, *one_dtp;             // route.one: scratch of the persistent launch, and its d_t rows (backward)
     float* wide;                      // route.wide: the spectrum split into ring pieces (forward, K = C = 256)
 };
 DiffuseWs diffuse_layout(Bump& b, const dn_mesh_batch_t* mb, int C, const DiffuseRoute& r, bool fwd, bool bwd) {
     DiffuseWs w; memset(&w, 0, sizeof(w));
     w.partial = b.f((size_t)mb->n_chunks * mb->k_eig * C); w.spec = b.f((size_t)mb->n_mesh * mb->k_eig * C);
     if (bwd) w.dtp = b.f((size_t)dn_spec_bwd_dt_rows(mb->n_mesh, mb->k_eig) * C);
-    if (r.one) w.one = b.f(dn_diffuse_ws_bytes(mb->df_n_wg, mb->df_n_groups, mb->n_mesh) / sizeof(float));      // (the hybrid form uses both sets)
-    if (r.one && bwd) w.one_dtp = b.f((size_t)diffuse_dt_rows(mb) * C);
     if (r.wide && fwd) w.wide = b.f(dn_backproject_wide_ws_floats(mb->n_mesh, mb->k_eig, C));
     return w;
 }
-// one persistent launch (dn_diffuse.hip, both products on the 3-term engine, as the three-launch form runs them by default) when the batch
-// carries its plan and the caller allows it (one_ok: no product asked onto the split-fp16 engine, which that form does not have) -- else
 // projection, spectral step, back-projection.  tob / fromb: engines of the two products, fromb.o receives max |xd| on every route; spec_amax
 // receives max |ys|; ysp, ysa (spectral-gradient form): the spectrum as weight pieces + per-mesh magnitudes INSTEAD of a back-projection
 int diffuse_fwd(const dn_mesh_batch_t* mb, const DiffuseRoute& r, const DiffuseWs& w, const float* x, const float* time, int C, float* xs, float* xd,
-                hipStream_t st, bool one_ok, const F16& tob = F16(), const F16& fromb = F16(), float* spec_amax = nullptr, float* ysp = nullptr,
+                hipStream_t st, const F16& tob = F16(), const F16& fromb = F16(), float* spec_amax = nullptr, float* ysp = nullptr,
                 float* ysa = nullptr) {
-    if (r.one && one_ok && diffuse_aligned(x, xd, xs, mb->evecs, time, mb->evals)) {
-        DfLaunch L = diffuse_new(mb, w.one);
-        L.x = x; L.time = time; L.xs = xs; L.out = xd; L.out_amax = fromb.o;
-        return dn_launch_diffuse(L, st);
-    }
     DN_CHECK(to_basis_partials(mb, x, C, true, w.partial, st, tob));
     DN_CHECK(dn_launch_spec_fwd(w.partial, mb->mesh_chunk_off, mb->evals, time, xs, w.spec, mb->n_mesh, mb->k_eig, C, st, spec_amax));
     // (spectral form: no back-projection launch, the chained kernel multiplies [evecs | gradX evecs | gradY evecs] by the spectrum itself)
@@ -355,20 +331,13 @@ int diffuse_fwd(const dn_mesh_batch_t* mb, const DiffuseRoute& r, const DiffuseW
 }
 // d_x = add + (diffusion backward of d_xd), d_time; add may be null.  defer (block): the d_t rows join these deferred sums, which are launched here
 int diffuse_bwd(const dn_mesh_batch_t* mb, const DiffuseRoute& r, const DiffuseWs& w, const float* d_xd, const float* xs, const float* time, int C,
-                const float* add, float* d_x, float* d_time, hipStream_t st, bool one_ok, const F16& tob = F16(), const F16& fromb = F16(),
+                const float* add, float* d_x, float* d_time, hipStream_t st, const F16& tob = F16(), const F16& fromb = F16(),
                 float* spec_amax = nullptr, MrJobs* defer = nullptr) {
     const int K = mb->k_eig;
     auto dt_sum = [&](const float* rows, int n) {
         if (defer && defer->push(rows, n, C, d_time)) return 0;
         return dn_launch_reduce(rows, d_time, n, C, C, st);
     };
-    if (r.one && one_ok && diffuse_aligned(d_xd, d_x, xs, mb->evecs, time, add)) {      // one launch (3-term engine throughout) + the d_t row sum
-        DfLaunch L = diffuse_new(mb, w.one);
-        L.bwd = 1; L.x = d_xd; L.time = time; L.xs = const_cast<float*>(xs); L.out = d_x; L.add = add; L.dt_part = w.one_dtp; L.out_amax = fromb.o;
-        DN_CHECK(dn_launch_diffuse(L, st));
-        DN_CHECK(dt_sum(w.one_dtp, diffuse_dt_rows(mb)));
-        return defer ? dn_launch_multi_reduce(*defer, st) : 0;
-    }
     DN_CHECK(to_basis_partials(mb, d_xd, C, false, w.partial, st, tob));
     if (dn_spec_bwd_fused_ok(w.partial, time, xs, w.spec, w.dtp, C)) {
         // one launch: per-mesh sums of the partials, exp(-lambda t), d_t contributions [mesh, eigenvalue group][C]
@@ -459,7 +428,7 @@ int dn_prof_read(int kind, double* out) {
     return 0;
 }
 const char* dn_prof_kind_name(int kind) {
-    static const char* names[DN_K_COUNT] = {"rowgemm_kernel<*,1>", "rowgemm_kernel<*,2>", "tngemm_kernel", "spmm_kernel", "small", "chain_fwd_kernel", "chain_bwd_kernel", "diffuse_kernel", "tngemm_x3_multi_kernel", "tngemm_da_kernel", "backproject_kernel", "spectral_apply_kernel"};
+    static const char* names[DN_K_COUNT] = {"rowgemm_kernel<*,1>", "rowgemm_kernel<*,2>", "tngemm_kernel", "spmm_kernel", "small", "chain_fwd_kernel", "chain_bwd_kernel", "tngemm_x3_multi_kernel", "tngemm_da_kernel", "backproject_kernel", "spectral_apply_kernel"};
     return (kind >= 0 && kind < DN_K_COUNT) ? names[kind] : "";
 }
 
@@ -481,7 +450,8 @@ int dn_tn_target_chunks_k(int k_eig) { return (k_eig >= 256 ? 1 : 2) * dn_num_cu
 int dn_diffusion_plan_wgs(void) { return dn_num_cus(); }
 int dn_diffusion_plan(const int32_t* sizes, int n_mesh, int n_wg, int n_groups, dn_tile_t* plan) {
     if (!sizes || !plan) return 0;
-    return dn_diffuse_plan_host(sizes, n_mesh, n_wg, n_groups > 0 ? n_groups : opt(O_DIFFUSE_GROUPS), reinterpret_cast<DnTile*>(plan));
+    (void)n_groups;      // reserved (the archived one-launch operator dealt a batch into several groups); the plan is one group
+    return dn_diffuse_plan_host(sizes, n_mesh, n_wg, reinterpret_cast<DnTile*>(plan));
 }
 
 // ------------------------------------------------------------------ to_basis / from_basis
@@ -511,7 +481,7 @@ int dn_diffusion_fwd_f32(const dn_mesh_batch_t* mb, const float* x, const float*
     Bump b(ws, ws_bytes);
     const DiffuseWs w = diffuse_layout(b, mb, C, r, true, false);
     if (!b.ok) return DN_ERR_INVALID;
-    return diffuse_fwd(mb, r, w, x, time, C, xs, xd, S(stream), time != nullptr);
+    return diffuse_fwd(mb, r, w, x, time, C, xs, xd, S(stream));
 }
 int dn_diffusion_bwd_f32(const dn_mesh_batch_t* mb, const float* d_xd, const float* xs, const float* time, int C,
                          const float* d_x_add, float* d_x, float* d_time, void* ws, size_t ws_bytes, void* stream) {
@@ -519,7 +489,7 @@ int dn_diffusion_bwd_f32(const dn_mesh_batch_t* mb, const float* d_xd, const flo
     Bump b(ws, ws_bytes);
     const DiffuseWs w = diffuse_layout(b, mb, C, r, false, true);
     if (!b.ok) return DN_ERR_INVALID;
-    return diffuse_bwd(mb, r, w, d_xd, xs, time, C, d_x_add, d_x, d_time, S(stream), xs != nullptr);
+    return diffuse_bwd(mb, r, w, d_xd, xs, time, C, d_x_add, d_x, d_time, S(stream));
 }
 
 // ------------------------------------------------------------------ spectral-gradient operands (dn_spectral.hip)
@@ -701,7 +671,7 @@ struct BlockRoute {
     // half per wave at every size measured, the backward up to ~100k rows.
     int hh;
     // The spectral-gradient form of the chained forward (dn_spectral.hip, dn_chain.hip KE > 0): batches that carry the packed operands, shapes the
-    // kernel is instantiated for, one 16-row half per wave (the forward's form up to 262144 rows); not with the one-launch diffusion operator.
+    // kernel is instantiated for, one 16-row half per wave (the forward's form up to 262144 rows).
     // Option "spectral_grad": 1 (default) = the inference forward at every size, the training forward up to 65536 rows; 2 = both at every size; 0 = never.
     // Measured (tools/kbench block_inf / block_fwd, us, spectral / gather form, same box; profiles/r06_sg_sweep.txt):
     //     vertices      7k          20k         40k         80k         160k        240k       64 x 2k
@@ -711,7 +681,7 @@ struct BlockRoute {
     // kernel (13 instead of 10 arrays of [V, C] through it) and is level with back-projection + gather from ~80k rows on (bench.py headline, two
     // runs each on one box: 30.82 / 30.85 M vertices/s against 31.02 / 31.02).
     bool sg;
-    DiffuseRoute d;     // one-launch diffusion, direct and wide back-projection
+    DiffuseRoute d;     // direct and wide back-projection
 };
 static BlockRoute block_route(const dn_mesh_batch_t* mb, const dn_block_params_t* p, int kind) {
     BlockRoute r;
@@ -734,7 +704,7 @@ static BlockRoute block_route(const dn_mesh_batch_t* mb, const dn_block_params_t
     r.sg = o && kind < 2 && (o >= 2 || (p->C < 256 && (kind == 0 || mb->v_total <= 65536))) && mb->sg_pack && mb->sg_units && mb->sg_amax && mb->sg_n_units > 0 &&
            al16(mb->sg_pack) && al16(mb->sg_amax) &&
            mb->sg_n_units <= 100 * dn_num_cus() &&      // (a workgroup's pass table lives in LDS: DN_CH_SG_MAXP = 64 passes of 2 x CUs workgroups)
-           r.chain && dn_chain_sg_eligible(p->C, mb->k_eig, p->with_grad, r.hh) && !r.d.one;
+           r.chain && dn_chain_sg_eligible(p->C, mb->k_eig, p->with_grad, r.hh);
     return r;
 }
 static bool chain_aligned(const dn_block_params_t* p, const dn_block_saved_t* sv, const float* a, const float* b_, const float* c = nullptr, const float* d = nullptr) {
@@ -902,7 +872,7 @@ int dn_block_fwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, cons
         tob = f16_of(m.ev_amax, m.in_amax); tob.b.mul = m.ms_amax; tob = f16_if(F16_TOB, tob);
         fromb = f16_if(F16_FROMB, f16_of(m.ev_amax, aw + AW_YS, sw + SW_XD));
     } else if (chain) fromb.o = sw + SW_XD;                         // (the chained kernel scales xd by its magnitude)
-    DN_CHECK(diffuse_fwd(mb, r.d, w.d, x, p->time, C, w.xs, w.xd, st, !(f16 && (f16_mask() & (F16_TOB | F16_FROMB))), tob, fromb,
+    DN_CHECK(diffuse_fwd(mb, r.d, w.d, x, p->time, C, w.xs, w.xd, st, tob, fromb,
                          (f16 && (f16_mask() & F16_FROMB)) ? aw + AW_YS : nullptr,      // only the split-fp16 back-projection needs max |ys|
                          sg ? w.ysp : nullptr, sg ? w.ysa : nullptr));
     // ---- row work, chained: gather -> gradient features -> MiniMLP + residual in one launch (layers.py:213-239)
@@ -1119,7 +1089,7 @@ int dn_block_bwd_f32(const dn_mesh_batch_t* mb, const dn_block_params_t* p, cons
     // ---- diffusion backward: its d_t rows join the deferred sums, which go out there
     F16 tob, fromb;
     if (f16) { tob = f16_if(F16_TOB_B, f16_of(m.ev_amax, aw + AW_MISC)); fromb = f16_if(F16_FROMB_B, f16_of(m.ev_amax, aw + AW_YS, gr->d_x_amax)); }
-    return diffuse_bwd(mb, r.d, w.d, w.d_xd, sv->xs, p->time, C, w.d_xacc, gr->d_x, gr->d_time, st, !(f16 && (f16_mask() & F16_TOB_B)), tob, fromb,
+    return diffuse_bwd(mb, r.d, w.d, w.d_xd, sv->xs, p->time, C, w.d_xacc, gr->d_x, gr->d_time, st, tob, fromb,
                        f16 ? aw + AW_YS : nullptr, &jobs);
 }
 

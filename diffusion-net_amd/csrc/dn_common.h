@@ -211,7 +211,7 @@ __device__ __forceinline__ float4 dn_load_f4_nt(const float* p) {
 #endif
 }
 // L1-bypassing ("sc1") 8-byte loads: agent-scope relaxed atomics.  What a workgroup reads of another workgroup's write-through (sc1)
-// stores inside ONE launch (dn_diffuse.hip): MI355X_MICROARCH.md, inter-workgroup visibility -- "sc1 loads may replace the acquire only
+// stores inside ONE launch: MI355X_MICROARCH.md, inter-workgroup visibility -- "sc1 loads may replace the acquire only
 // when the producer stored sc1".  Compiler-tracked (no inline asm: an asm load's destination may be spilled before the data arrives).
 __device__ __forceinline__ float2 dn_ld2_coherent(const float* p) {
 #ifdef DN_EMULATE
@@ -588,32 +588,9 @@ int dn_launch_spec_pieces(const float* ys, int n_mesh, int K, int C, uint4* out,
 int dn_launch_spectral_apply(const ChainArgs& a, int C, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------
-// one-launch learned-time diffusion, forward and backward (dn_diffuse.hip; K = C = 128)
+// direct back-projection of the learned-time diffusion (dn_diffuse.hip; K = C = 128) and its work plan
 // ---------------------------------------------------------------------------------------
-#define DN_DF_MAX_GROUPS 4
-#define DN_DF_MAX_SCHED 12
-enum { DN_DF_OP_P1 = 1, DN_DF_OP_R = 2, DN_DF_OP_P3 = 3 };
-enum { DN_DF_FLAG_DEFER = 1,       // an arrival is posted from inside the NEXT projection loop (its stores drain under that loop's loads)
-       DN_DF_FLAG_SOLO_R = 2,      // tests: half of the workgroups pretend their poll for the partials ran out
-       DN_DF_FLAG_SOLO_P3 = 4 };   // tests: the other half pretend their poll for the scaled spectrum ran out
-struct DfLaunch {
-    const DnTile* plan;            // device: [n_groups * n_wg], dn_diffuse_plan_host()
-    int n_wg, n_groups, n_mesh;
-    const float* evecs; const float* x; const float* mass; const float* evals; const float* time;
-    float* xs;                     // forward: receives the unscaled spectrum (may be null); backward: the forward's spectrum (read)
-    float* out; const float* add;  // backward: out = add + mass * (...) (add may be null)
-    float* dt_part;                // backward: [dn_diffuse_dt_rows()][128]
-    float* out_amax;               // optional: max |out| is accumulated into it (atomic max)
-    void* ws;                      // dn_diffuse_ws_bytes()
-    int bwd, order, flags;
-    int split;                     // bit i: kernel boundary after schedule step i (0: one launch)
-    long long acct_rows;           // host-side accounting only
-};
-size_t dn_diffuse_ws_bytes(int n_wg, int n_groups, int n_mesh);
-int dn_diffuse_dt_rows(int n_wg, int n_groups);
-int dn_diffuse_schedule(int G, int order, int* sched);
-int dn_diffuse_plan_host(const int* sizes, int n_mesh, int n_wg, int n_groups, DnTile* plan);
-int dn_launch_diffuse(const DfLaunch& L, hipStream_t stream);
+int dn_diffuse_plan_host(const int* sizes, int n_mesh, int n_wg, DnTile* plan);
 int dn_launch_backproject(const DnTile* plan, int n_wg, const float* evecs, const float* ys, float* out, const float* add, const float* mass,
                           float* out_amax, double acct_rows, hipStream_t stream, int f16 = 0, const DnAmax* a_amax = nullptr, const DnAmax* b_amax = nullptr);
 // dn_backproject_wide.hip: the forward back-projection at K = C = 256 (3-term engine, the spectrum streamed through an LDS-DMA ring)
@@ -758,7 +735,7 @@ int dn_launch_tngemm_multi(const TnArgs* gs, const int* nchunks, int count, hipS
 // hipEvents on its own stream and summed per kernel family.  Off by default; compiled out of the
 // emulator build.
 // ---------------------------------------------------------------------------------------
-enum { DN_K_ROWGEMM = 0, DN_K_ROWGEMM_DUAL = 1, DN_K_TNGEMM = 2, DN_K_SPMM = 3, DN_K_SMALL = 4, DN_K_CHAIN = 5, DN_K_CHAIN_BWD = 6, DN_K_DIFFUSE = 7, DN_K_TN_MULTI = 8, DN_K_TN_DA = 9, DN_K_BACKPROJECT = 10, DN_K_SPECTRAL = 11, DN_K_COUNT = 12 };   // one kind per KERNEL (rocprof name), except the small-kernel bucket
+enum { DN_K_ROWGEMM = 0, DN_K_ROWGEMM_DUAL = 1, DN_K_TNGEMM = 2, DN_K_SPMM = 3, DN_K_SMALL = 4, DN_K_CHAIN = 5, DN_K_CHAIN_BWD = 6, DN_K_TN_MULTI = 7, DN_K_TN_DA = 8, DN_K_BACKPROJECT = 9, DN_K_SPECTRAL = 10, DN_K_COUNT = 11 };   // one kind per KERNEL (rocprof name), except the small-kernel bucket
 #ifdef DN_EMULATE
 static inline void dn_prof_begin(int, hipStream_t) {}
 static inline void dn_prof_end(int, hipStream_t, double, double) {}

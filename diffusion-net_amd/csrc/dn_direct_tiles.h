@@ -1,4 +1,4 @@
-// dn_direct_tiles.h -- "direct" row product for K = 128 (the back-projection phase of the one-launch diffusion operator, dn_diffuse.hip): out[r, 0..127] = sum_k A[r, k] B[k, n] with the long operand A read straight
+// dn_direct_tiles.h -- "direct" row product for K = 128 (the back-projection launch of the diffusion operator, dn_diffuse.hip): out[r, 0..127] = sum_k A[r, k] B[k, n] with the long operand A read straight
 // from global memory into MFMA fragments (no LDS round trip, no barrier) and the 128 x 128 operand B split once per workgroup into
 // fragment-ordered bf16 planes resident in LDS.  Developed and measured as tools/experiments/rowgemm_direct (see its README).
 //   * unit = 16 rows x 128 columns per wave, eight 16x16 accumulators, v_mfma_f32_16x16x32_bf16 with the operands swapped
@@ -251,11 +251,4 @@ __device__ __forceinline__ float rd_rows_run(const RgArgs& g, const unsigned cha
         }
     }
     return om;
-}
-template <int MODE>
-__device__ __forceinline__ float rd_run_rows(const RgArgs& g, const unsigned char* sB, const float* ap, int ald, int rs, int re, int n0,
-                                             int wave, int lane) {
-    RdStart S;
-    rd_rows_begin(ap, ald, rs, re, wave, lane, S);
-    return rd_rows_run<MODE>(g, sB, ap, ald, rs, re, n0, lane, S);
 }

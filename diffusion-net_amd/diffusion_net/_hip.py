@@ -171,7 +171,7 @@ def get_option(name: str) -> int:
     return v.value
 
 
-DIFFUSION_MAX_GROUPS = 4    # include/diffnet_hip.h: DN_DIFFUSION_MAX_GROUPS
+DIFFUSION_MAX_GROUPS = 1    # include/diffnet_hip.h: DN_DIFFUSION_MAX_GROUPS
 
 
 def _use_library_for_tests(path, allow_host_tensors):

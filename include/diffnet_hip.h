@@ -64,8 +64,8 @@ typedef struct dn_mesh_batch {
      * summed as sum_j |gradX_ij| resp. sum_j |gradY_ij| (the larger of the two row sums): max |gradX x|, |gradY x| <= it * max |x| is
      * the magnitude bound the split-fp16 gradient-feature products scale by (about 3x the true maximum on a mesh).  NULL: measured. */
     const float* grad_norm;
-    /* Optional (round 5): the work plan of the one-launch diffusion operator (dn_diffusion_plan()): device array of df_n_groups * df_n_wg
-     * entries.  NULL / 0: the diffusion runs as three launches (projection, spectral step, back-projection). */
+    /* Optional (round 5): the work plan of the diffusion's direct back-projection launch (dn_diffusion_plan()): device array of df_n_wg
+     * entries; df_n_groups is 1 when a plan is attached.  NULL / 0: the back-projection is the row GEMM. */
     const dn_tile_t* df_plan; int32_t df_n_wg, df_n_groups;
     /* Optional (round 6): the spectral-gradient operands of the batch (dn_spectral_pack_f32): the spatial gradient apply re-associated
      * through the eigenbasis, gradX (evecs ys) = (gradX evecs) ys.  sg_pack: [evecs | gradX evecs | gradY evecs] as fp16 (hi, lo) operand
@@ -163,13 +163,8 @@ int dn_tn_target_chunks_k(int k_eig);   /* (round 6) the same for a batch of k_e
  *        "f16" (1)              split-fp16 matrix engine for the row products of the fused block (0: split-bf16 everywhere)
  *        "f16_mask" (188)       product classes on the split-fp16 engine (diagnostic bit mask, dn_api.hip)
  *        "f16_wgrad" (0)        parameter-gradient products on the split-fp16 engine (diagnostic)
- *        "diffuse" (2)          batches that carry a plan (dn_diffusion_plan), K = C = 128: 2 = the back-projection of the diffusion is the direct
- *                               row-product launch (dn_diffuse.hip: backproject_kernel); 1 = the whole operator as ONE persistent launch
- *                               (diffuse_kernel; any number of groups); 0 = the wave-specialised row GEMM of the earlier rounds
- *        "diffuse_groups" (1)   mesh groups dn_diffusion_plan() deals the batch into when asked for 0 (the direct back-projection needs 1)
- *        "diffuse_order" (0)    schedule of the one-launch operator (0: interleaved groups, 1: projections first)
- *        "diffuse_flags" (1)    one-launch kernel: bit 0 = arrivals posted from inside the next projection loop; bits 1, 2 = tests (forced solo path)
- *        "diffuse_split" (0)    one-launch kernel: bit i = a kernel boundary after schedule step i (measurements)
+ *        "diffuse" (2)          batches that carry a plan (dn_diffusion_plan), K = C = 128: non-zero = the back-projection of the diffusion is the
+ *                               direct row-product launch (dn_diffuse.hip: backproject_kernel); 0 = the wave-specialised row GEMM of the earlier rounds
  *        "spectral_grad" (1)    batches that carry spectral-gradient operands (dn_spectral_pack_f32): the chained forward kernel computes xd, gx, gy
  *                               from them (no back-projection launch, no CSR gather) -- 1 = in the inference forward at every size and in the training
  *                               forward up to 65536 rows, both at C <= 128 (where it measures faster), 2 = wherever a form exists (incl. the two-launch
@@ -179,7 +174,7 @@ int dn_get_option(const char* name, int* value);
 
 /* ---- opt-in per-kernel timing for benchmarks (no reference counterpart; the one piece of mutable global
  *      state, off by default): every launch is bracketed by hipEvents on its stream and summed per kernel
- *      kernel kind in [0, 12) (dn_prof_kind_name(kind) is "" past the last one).  read: out[0..3] = {ms, launches, algorithmic flops, algorithmic bytes}. */
+ *      kernel kind in [0, 11) (dn_prof_kind_name(kind) is "" past the last one).  read: out[0..3] = {ms, launches, algorithmic flops, algorithmic bytes}. */
 int dn_prof_enable(int on);
 int dn_prof_reset(void);
 int dn_prof_read(int kind, double* out);
@@ -197,13 +192,13 @@ int dn_from_basis_f32(const dn_mesh_batch_t* mb, const float* spec, int C, int s
 /* ---- LearnedTimeDiffusion.forward, method='spectral' (layers.py:44-67) and its gradient.
  *      fwd: xs = to_basis(x), xd = from_basis(exp(-evals*time) * xs).
  *      bwd: d_x = d_x_add + mass * (evecs (coef * evecs^T d_xd)), d_time[c] = -sum lambda*coef*xs*(evecs^T d_xd). */
-/*      dn_diffuse.hip (direct back-projection launch; one-launch form): taken when mb->df_plan is set, k_eig = C = 128 and every operand is
+/*      dn_diffuse.hip (direct back-projection launch): taken when mb->df_plan is set, k_eig = C = 128 and every operand is
  *      16-byte aligned (option "diffuse").
  *      dn_diffusion_plan_wgs(): workgroups the plan should be made for on the current device (one per CU).
- *      dn_diffusion_plan(): HOST arithmetic -- sizes[n_mesh] = vertices per mesh in row order; n_groups = 0: the "diffuse_groups" option;
- *      plan: HOST array of DN_DIFFUSION_MAX_GROUPS * n_wg entries; returns the number of groups used (0: batch not plannable, leave
- *      df_plan NULL).  The caller uploads plan[0 .. groups * n_wg) and sets df_plan / df_n_wg / df_n_groups. */
-#define DN_DIFFUSION_MAX_GROUPS 4
+ *      dn_diffusion_plan(): HOST arithmetic -- sizes[n_mesh] = vertices per mesh in row order; n_groups: reserved, pass 0 (ignored);
+ *      plan: HOST array of DN_DIFFUSION_MAX_GROUPS * n_wg entries; returns 1, or 0: batch not plannable, leave df_plan NULL.  The
+ *      caller uploads plan[0 .. n_wg) and sets df_plan, df_n_wg, df_n_groups = 1 and df_v_total. */
+#define DN_DIFFUSION_MAX_GROUPS 1
 int dn_diffusion_plan_wgs(void);
 int dn_diffusion_plan(const int32_t* sizes, int n_mesh, int n_wg, int n_groups, dn_tile_t* plan);
 size_t dn_diffusion_workspace_bytes(const dn_mesh_batch_t* mb, int C);

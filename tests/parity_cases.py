@@ -275,15 +275,13 @@ def run_block_flags(device, sizes=(300, 140), C=128, seed=9):
 
 
 # ------------------------------------------------------------------------------------------
-# one-launch diffusion operator (dn_diffuse.hip) vs the oracle and vs the three-launch form
+# diffusion operator: both back-projection routes (row GEMM, direct launch of dn_diffuse.hip) vs the oracle and vs each other
 # ------------------------------------------------------------------------------------------
-def run_diffuse_fused(device, sizes=(300, 140, 210), seed=3, configs=((1, 0, 1), (3, 0, 1), (2, 1, 0), (3, 0, 7)), reps=2,
-                      fwd_tol=None, grad_tol=None):
-    """LearnedTimeDiffusion forward + backward at K = C = 128 through ops.DiffusionFn: the persistent one-launch kernel for every
-    (groups, schedule order, flags) in ``configs`` against the fp32 oracle (layers.py:44-67) and against the three-launch form of the same
-    library; flags & 6 force the "solo" recovery path (a workgroup whose poll ran out recomputes its mesh's partial sums itself), which must
-    reproduce the cooperative result BIT FOR BIT.  ``reps`` different inputs go through the SAME workspace addresses (stale-line check of
-    the inter-workgroup hand-offs: a reader that saw the previous repetition's partials would be far outside the tolerance)."""
+def run_diffusion_routes(device, sizes=(300, 140, 210), seed=3, reps=2, fwd_tol=None, grad_tol=None):
+    """LearnedTimeDiffusion forward + backward at K = C = 128 through ops.DiffusionFn against the fp32 oracle (layers.py:44-67): with the
+    row-GEMM back-projection (option "diffuse" = 0) and with the shipped direct back-projection launch (option "diffuse" = 2, which must have
+    run -- its result is not bitwise the row GEMM's -- and agrees with it to 5e-6).  ``reps`` different inputs go through the SAME workspace
+    addresses."""
     from diffusion_net import _hip
     fwd_tol = FWD_TOL if fwd_tol is None else fwd_tol
     grad_tol = GRAD_TOL if grad_tol is None else grad_tol
@@ -311,9 +309,8 @@ def run_diffuse_fused(device, sizes=(300, 140, 210), seed=3, configs=((1, 0, 1),
                          for i, m in enumerate(meshes)], 0)
         (ref * w).sum().backward()
         refs.append((ref.detach(), xr.grad, tr.grad))
-    names = ("diffuse", "diffuse_groups", "diffuse_order", "diffuse_flags", "diffuse_split")
-    saved = {k: _hip.get_option(k) for k in names}
-    worst = {"fwd": 0.0, "d_x": 0.0, "d_t": 0.0, "vs3_fwd": 0.0}
+    saved = _hip.get_option("diffuse")
+    worst = {"fwd": 0.0, "d_x": 0.0, "d_t": 0.0}
     try:
         _hip.set_option("diffuse", 0)
         mb0 = pack(meshes, device, chunk_rows=64)
@@ -322,7 +319,6 @@ def run_diffuse_fused(device, sizes=(300, 140, 210), seed=3, configs=((1, 0, 1),
             assert helpers.rel_max(xd, rx) < fwd_tol and helpers.rel_l2(dx, rdx) < grad_tol and helpers.rel_l2(dt, rdt) < grad_tol
         # the shipped form: split-V projection + spectral step + the DIRECT back-projection launch (option "diffuse" = 2, one-group plan)
         _hip.set_option("diffuse", 2)
-        _hip.set_option("diffuse_groups", 1)
         mb2 = pack(meshes, device, chunk_rows=64)
         assert mb2.df_plan is not None and mb2._struct.df_n_groups == 1
         for r, inp in enumerate(inputs):
@@ -333,35 +329,9 @@ def run_diffuse_fused(device, sizes=(300, 140, 210), seed=3, configs=((1, 0, 1),
             assert not torch.equal(xd, three[r][0]), "direct and row-GEMM back-projection are bitwise equal: the direct kernel did not run"
             assert helpers.rel_max(xd, three[r][0]) < 5e-6
             worst["fwd"], worst["d_x"], worst["d_t"] = max(worst["fwd"], e[0]), max(worst["d_x"], e[1]), max(worst["d_t"], e[2])
-        coop = {}
-        for groups, order, flags in configs:
-            _hip.set_option("diffuse", 1)
-            _hip.set_option("diffuse_groups", groups)
-            _hip.set_option("diffuse_order", order)
-            _hip.set_option("diffuse_flags", flags)
-            mb = pack(meshes, device, chunk_rows=64)
-            assert mb.df_plan is not None and mb._struct.df_n_groups == min(groups, len(sizes)), "no diffusion plan on the batch"
-            for r, inp in enumerate(inputs):
-                xd, dx, dt = run(mb, *inp)
-                rx, rdx, rdt = refs[r]
-                e = (helpers.rel_max(xd, rx), helpers.rel_l2(dx, rdx), helpers.rel_l2(dt, rdt))
-                assert e[0] < fwd_tol and e[1] < grad_tol and e[2] < grad_tol, ("fused diffusion vs oracle", (groups, order, flags), r, e)
-                assert not torch.equal(xd, three[r][0]), "fused and three-launch diffusion are bitwise equal: the fused kernel did not run"
-                e3 = helpers.rel_max(xd, three[r][0])
-                assert e3 < 5e-6, ("fused vs three-launch diffusion", e3)
-                worst = {"fwd": max(worst["fwd"], e[0]), "d_x": max(worst["d_x"], e[1]), "d_t": max(worst["d_t"], e[2]), "vs3_fwd": max(worst["vs3_fwd"], e3)}
-                key = (mb._struct.df_n_groups, r)
-                if flags & 6:      # the solo path: the same bits as the cooperative run of the same plan
-                    if key in coop:
-                        for a, b, what in zip((xd, dx, dt), coop[key], ("x_diffuse", "d_x", "d_time")):
-                            assert torch.equal(a, b), ("solo path differs from the cooperative result", what, (groups, order, flags))
-                else:
-                    coop.setdefault(key, (xd, dx, dt))
     finally:
-        for k, v in saved.items():
-            _hip.set_option(k, v)
-    helpers.record_margin("diffuse_fused", device, sizes=list(sizes), configs=[list(c) for c in configs], fwd_rel_max=worst["fwd"],
-                          d_x_rel_l2=worst["d_x"], d_time_rel_l2=worst["d_t"], fused_vs_three_launch_fwd=worst["vs3_fwd"])
+        _hip.set_option("diffuse", saved)
+    helpers.record_margin("diffuse_fused", device, sizes=list(sizes), fwd_rel_max=worst["fwd"], d_x_rel_l2=worst["d_x"], d_time_rel_l2=worst["d_t"])
     return worst
 
 
@@ -670,7 +640,7 @@ def run_exact_workspace(device):
         run_ragged_net(device, sizes=(150, 130), K=128, C=128, N_block=1, chunk_rows=64)      # chained forward and backward, direct back-projection
         run_ragged_net(device, sizes=(130, 257, 64), chunk_rows=64)                            # unfused launches, C = 32, no split-fp16
         run_spectral_grad(device, sizes=(150, 193), N_block=1, dropout=False, chain_nw=2)      # spectral-gradient form and its reference form
-        run_diffuse_fused(device, sizes=(130, 700), seed=9, configs=((2, 0, 1),), reps=1)      # one-launch diffusion
+        run_diffusion_routes(device, sizes=(130, 700), seed=9, reps=1)      # diffusion entry points, direct back-projection
         run_ragged_net(device, sizes=(70, 45), K=32, C=256, N_block=1, empty_grad_rows=3, chunk_rows=64)      # C = 256 forward
         run_ops(device)                                                                        # the per-op entry points
 

@@ -62,12 +62,83 @@ def test_persistent_rowgemm_with_dropout_on_emulator(emu):
     parity_cases.run_ragged_net(emu, sizes=(300, 140), K=128, C=128, N_block=1, dropout=True, chunk_rows=64)
 
 
-def test_one_launch_diffusion_on_emulator(emu):
-    """dn_diffuse.hip (forward + backward, 1-3 mesh groups, both schedules, forced solo path) vs the oracle and the three-launch form; the
-    emulator runs the schedule one step per launch (its workgroups execute one after the other)."""
+def test_diffusion_routes_on_emulator(emu):
+    """The diffusion operator (forward + backward) with the row-GEMM and with the direct back-projection of dn_diffuse.hip vs the oracle and
+    vs each other."""
     import parity_cases
-    parity_cases.run_diffuse_fused(emu)
-    parity_cases.run_diffuse_fused(emu, sizes=(130, 700), seed=9, configs=((2, 0, 1), (2, 0, 7)), reps=1)   # a small mesh next to a large one
+    parity_cases.run_diffusion_routes(emu)
+    parity_cases.run_diffusion_routes(emu, sizes=(130, 700), seed=9, reps=1)   # a small mesh next to a large one
+
+
+PLAN_SIZES = ((7000,), (130, 700), (300, 140, 210), tuple(9000 + 137 * i for i in range(16)), (64,) * 40)
+
+
+def _diffusion_plan(sizes, n_wg, n_groups=0, pad=8):
+    """dn_diffusion_plan() into a buffer of n_wg + pad sentinel rows: (return value, the first n_wg rows, the rows behind them)."""
+    import numpy as np
+    from diffusion_net import _hip
+    arr = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+    buf = np.full((n_wg + pad, 4), 0x5A5A5A5A, dtype=np.int32)
+    ret = int(_hip.lib().dn_diffusion_plan(arr.ctypes.data, len(arr), n_wg, n_groups, buf.ctypes.data))
+    return ret, buf[:n_wg], buf[n_wg:]
+
+
+@pytest.mark.parametrize("n_wg", [256, 8])
+@pytest.mark.parametrize("sizes", PLAN_SIZES, ids=lambda s: "%dx%d" % (len(s), s[0]))
+def test_diffusion_plan_one_group(emu, sizes, n_wg):
+    """Host arithmetic of dn_diffusion_plan(): one group of n_wg entries {row0, nrows, mesh, aux} that partitions every mesh's rows in row
+    order, splits on 16-row boundaries, and ignores n_groups.  A batch of more meshes than workgroups is not plannable (returns 0): of the
+    size lists here that is the 16- and the 40-mesh one at n_wg = 8."""
+    import numpy as np
+    ret, plan, behind = _diffusion_plan(sizes, n_wg)
+    assert (behind == 0x5A5A5A5A).all(), "wrote past n_wg entries"
+    if len(sizes) > n_wg:
+        assert ret == 0
+        return
+    assert ret == 1
+    assert not (plan == 0x5A5A5A5A).all(axis=1).any(), "fewer than n_wg entries written"
+    live = plan[plan[:, 2] >= 0]
+    idle = plan[len(live):]
+    assert (idle[:, 2] == -1).all() and (idle[:, 1] == 0).all()          # the live entries come first, the idle ones carry no rows
+    assert (live[:, 1] >= 1).all()
+    assert live[0, 0] == 0 and (live[:-1, 0] + live[:-1, 1] == live[1:, 0]).all() and live[-1, 0] + live[-1, 1] == sum(sizes)   # row order, no gap, no overlap
+    start, slot = 0, 0
+    for m, v in enumerate(sizes):
+        mine = live[live[:, 2] == m]
+        c = len(mine)
+        assert c >= 1 and (live[slot:slot + c, 2] == m).all()                # consecutive entries, meshes in order
+        assert mine[0, 0] == start and int(mine[:, 1].sum()) == v            # exactly this mesh's rows
+        assert (mine[:, 3] == slot * 1024 + c).all()                         # aux = first_slot * 1024 + count
+        for j in range(c - 1):                                               # split points inside the mesh
+            e = int(mine[j, 0] + mine[j, 1]) - start
+            forced = mine[j, 1] == 1 or v - e == c - 1 - j                   # "at least one row per workgroup", from either side
+            assert e % 16 == 0 or forced, (m, j, e)
+        start, slot = start + v, slot + c
+    for n_groups in (1, 3):
+        r2, p2, b2 = _diffusion_plan(sizes, n_wg, n_groups)
+        assert r2 == 1 and np.array_equal(p2, plan) and (b2 == 0x5A5A5A5A).all()
+    assert _diffusion_plan((100,) * 300, 256)[0] == 0                        # more meshes than workgroups
+    assert _diffusion_plan(sizes[:1] + (0,) + sizes[1:], n_wg)[0] == 0       # an empty mesh
+
+
+def test_retired_diffusion_options_are_refused(emu):
+    """The options of the archived one-launch operator are unknown names to dn_set_option / dn_get_option; "diffuse" still round-trips."""
+    import ctypes as C
+    from diffusion_net import _hip
+    L = _hip.lib()
+    v = C.c_int(-7)
+    for name in (b"diffuse_groups", b"diffuse_order", b"diffuse_flags", b"diffuse_split"):
+        assert L.dn_set_option(name, 1) != 0, name
+        assert L.dn_get_option(name, C.byref(v)) != 0 and v.value == -7, name
+    old = _hip.get_option("diffuse")
+    try:
+        prev = old
+        for x in (0, 1, 2):
+            assert _hip.set_option("diffuse", x) == prev and _hip.get_option("diffuse") == x
+            prev = x
+    finally:
+        _hip.set_option("diffuse", old)
+    assert _hip.get_option("diffuse") == old == 2
 
 
 def test_chain_probes_against_the_oracle_on_emulator(emu):

@@ -49,15 +49,13 @@ def test_exact_workspace(dev):
     parity_cases.run_exact_workspace(dev)
 
 
-def test_one_launch_diffusion(dev):
-    """dn_diffuse.hip on the device (256 co-resident workgroups, real inter-workgroup hand-offs): forward + backward against the oracle and the
-    three-launch form for 1-4 mesh groups, both schedules, deferred / immediate arrivals, the forced solo path (bit for bit the cooperative
-    result), several inputs through the same workspace addresses, ragged and tiny meshes."""
+def test_diffusion_routes(dev):
+    """The diffusion operator on the device, forward + backward, with the row-GEMM and with the direct back-projection launch of dn_diffuse.hip
+    against the oracle and against each other: several inputs through the same workspace addresses, ragged and tiny meshes."""
     import parity_cases
-    parity_cases.run_diffuse_fused(dev, sizes=(3000, 1400, 2100, 129, 5000), seed=3,
-                                   configs=((1, 0, 1), (2, 0, 1), (3, 0, 1), (4, 0, 1), (3, 1, 1), (3, 0, 0), (2, 0, 7), (3, 0, 7)), reps=3)
-    parity_cases.run_diffuse_fused(dev, sizes=(7000,), seed=4, configs=((1, 0, 1), (1, 0, 7)), reps=2)          # one mesh: BASELINE config 2
-    parity_cases.run_diffuse_fused(dev, sizes=tuple(9000 + 137 * i for i in range(16)), seed=5, configs=((3, 0, 1), (2, 0, 1)), reps=2)   # headline batch
+    parity_cases.run_diffusion_routes(dev, sizes=(3000, 1400, 2100, 129, 5000), seed=3, reps=3)
+    parity_cases.run_diffusion_routes(dev, sizes=(7000,), seed=4, reps=2)          # one mesh: BASELINE config 2
+    parity_cases.run_diffusion_routes(dev, sizes=tuple(9000 + 137 * i for i in range(16)), seed=5, reps=2)   # headline batch
 
 
 @pytest.mark.parametrize("outputs_at", ["vertices", "faces", "global_mean"])

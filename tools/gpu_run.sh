@@ -1,10 +1,11 @@
 #!/bin/bash
 # ONE parameterised GPU script (replaces the per-experiment tools/gpu_r*.sh of rounds 3-4): gpurun -- 'bash tools/gpu_run.sh <section> ...'.
 # Every section writes under $DN_OUT_DIR (default: out/ in the repository) and prints a short summary.  Sections:
-#   df_sweep     kbench of the diffusion operator: three launches vs the one-launch kernel for 1-4 mesh groups, both schedules, deferred /
-#                immediate arrivals; forward + backward, fp64 spot checks
-#   df_trace     s_memtime phase timeline of the one-launch kernel (libdiffnet_hip_dftrace.so = make variant TAG=dftrace EXTRA=-DDN_DF_TRACE=1)
-#   df_small     the same comparison on one 7k-vertex mesh (BASELINE config 2) and on 64 x 2k meshes
+#   df_sweep     kbench of the diffusion operator without a plan (row-GEMM back-projection); forward + backward, fp64 spot checks
+#   df_modes     option "diffuse" = 0 / 2 on four batch shapes and in the block calls; workgroup start / end times of backproject_kernel
+#                (libdiffnet_hip_dftrace.so = make variant TAG=dftrace EXTRA=-DDN_DF_TRACE=1)
+#   df_small     df_sweep on one 7k-vertex mesh (BASELINE config 2), on 64 x 2k and on 4 x 40k meshes
+#                (the one-launch kernel these three sections once swept is archived: tools/experiments/diffusion_one_launch/)
 #   c256         BASELINE config 4's width: kbench block tables chained / unfused at C = 256, the C = 256 parity cases, bench.py --config cfg4
 #   kbench       block_inf / block_fwd / block_bwd / diffusion tables (tools/kbench --check)
 #   knn          ops.knn at the two find_knn workload shapes against chunked cdist + topk and the host KD-tree (tools/knn_timing.py)
@@ -21,25 +22,19 @@ KB="timeout 180 ./tools/kbench"
 sec=$1; shift
 case "$sec" in
 df_sweep)
-  { echo "== three launches"; $KB --ops diffusion,diffusion_bwd --check --reps 30 --no-plan | cut -c1-170
-    for g in 1 2 3 4; do for o in 0 1; do for f in 1 0; do
-      echo "== one launch: groups $g order $o flags $f"; $KB --ops diffusion,diffusion_bwd --check --reps 30 --groups $g --opt diffuse_order=$o --opt diffuse_flags=$f | grep -v "^#" | cut -c1-170
-    done; done; done; } 2>&1 | tee $OUT/df_sweep.txt ;;
-df_trace)
-  for g in ${1:-1 2 3}; do echo "== trace groups $g"; $KB --lib diffusion-net_amd/diffusion_net/libdiffnet_hip_dftrace.so --ops diffusion,diffusion_bwd --trace --reps 10 --groups $g | grep -v "^#" | cut -c1-260; done 2>&1 | tee $OUT/df_trace.txt ;;
+  { echo "== three launches"; $KB --ops diffusion,diffusion_bwd --check --reps 30 --no-plan | cut -c1-170; } 2>&1 | tee $OUT/df_sweep.txt ;;
 df_modes)
   { for shape in "--meshes 16 --verts 10000" "--meshes 1 --verts 7000" "--meshes 64 --verts 2000" "--meshes 1 --verts 160000"; do
-      for d in 0 2 1; do echo "== $shape: option diffuse=$d (0 row-GEMM back-projection, 2 direct back-projection launch, 1 one-launch kernel)"
-        $KB $shape --ops diffusion,diffusion_bwd --check --reps 40 --groups 1 --opt diffuse=$d | grep -v "^#" | cut -c1-170; done
+      for d in 0 2; do echo "== $shape: option diffuse=$d (0 row-GEMM back-projection, 2 direct back-projection launch)"
+        $KB $shape --ops diffusion,diffusion_bwd --check --reps 40 --opt diffuse=$d | grep -v "^#" | cut -c1-170; done
     done
-    for d in 0 2; do echo "== blocks, 16 x 10k, diffuse=$d"; $KB --ops block_inf,block_fwd,block_bwd --reps 30 --groups 1 --opt diffuse=$d | grep -v "^#" | cut -c1-120; done
-    for d in 0 2; do echo "== blocks, 1 x 7k, diffuse=$d"; $KB --meshes 1 --verts 7000 --ops block_inf,block_fwd,block_bwd --reps 50 --groups 1 --opt diffuse=$d | grep -v "^#" | cut -c1-120; done
-    echo "== back-projection kernel phase stamps (cycles: planes staged, rows done)"; $KB --lib diffusion-net_amd/diffusion_net/libdiffnet_hip_dftrace.so --ops diffusion,diffusion_bwd --trace --reps 5 --groups 1 | grep -v "^#" | cut -c1-60
+    for d in 0 2; do echo "== blocks, 16 x 10k, diffuse=$d"; $KB --ops block_inf,block_fwd,block_bwd --reps 30 --opt diffuse=$d | grep -v "^#" | cut -c1-120; done
+    for d in 0 2; do echo "== blocks, 1 x 7k, diffuse=$d"; $KB --meshes 1 --verts 7000 --ops block_inf,block_fwd,block_bwd --reps 50 --opt diffuse=$d | grep -v "^#" | cut -c1-120; done
+    echo "== back-projection kernel: workgroup start / end times"; $KB --lib diffusion-net_amd/diffusion_net/libdiffnet_hip_dftrace.so --ops diffusion,diffusion_bwd --trace --reps 5 | grep -v "^#" | cut -c1-200
   } 2>&1 | tee $OUT/df_modes.txt ;;
 df_small)
   { for shape in "--meshes 1 --verts 7000" "--meshes 64 --verts 2000" "--meshes 4 --verts 40000"; do
       echo "== $shape: three launches"; $KB $shape --ops diffusion,diffusion_bwd --check --reps 50 --no-plan | grep -v "^#" | cut -c1-170
-      for g in 1 2 3; do echo "== $shape: one launch, groups $g"; $KB $shape --ops diffusion,diffusion_bwd --check --reps 50 --groups $g | grep -v "^#" | cut -c1-170; done
     done; } 2>&1 | tee $OUT/df_small.txt ;;
 c256)
   { for c in 1 0; do echo "== 1 x 200k, C = K = 256, chain=$c"; $KB --meshes 1 --verts 200000 --C 256 --K 256 --ops block_inf,block_fwd --check --reps 10 --opt chain=$c | grep -v "^#" | cut -c1-170; done

@@ -78,7 +78,7 @@ static std::vector<float> host(const float* d, size_t n) { std::vector<float> v(
 
 int main(int argc, char** argv) {
     std::string libpath = "diffusion-net_amd/diffusion_net/libdiffnet_hip.so", ops = "all";
-    int n_mesh = 16, verts = 10000, C = 128, K = 128, reps = 20, chunk_rows = 0, df_groups = 0;
+    int n_mesh = 16, verts = 10000, C = 128, K = 128, reps = 20, chunk_rows = 0;
     bool check = false, trace = false, no_plan = false;
     std::vector<std::pair<std::string, int>> lib_opts;
     for (int i = 1; i < argc; ++i) {
@@ -87,7 +87,7 @@ int main(int argc, char** argv) {
         if (a == "--lib") libpath = nxt(); else if (a == "--meshes") n_mesh = atoi(nxt().c_str()); else if (a == "--verts") verts = atoi(nxt().c_str());
         else if (a == "--C") C = atoi(nxt().c_str()); else if (a == "--K") K = atoi(nxt().c_str()); else if (a == "--reps") reps = atoi(nxt().c_str());
         else if (a == "--ops") ops = nxt(); else if (a == "--check") check = true; else if (a == "--trace") trace = true; else if (a == "--chunk") chunk_rows = atoi(nxt().c_str());
-        else if (a == "--groups") df_groups = atoi(nxt().c_str()); else if (a == "--no-plan") no_plan = true;
+        else if (a == "--no-plan") no_plan = true;
         else if (a == "--opt") { const std::string kv = nxt(); const size_t eq = kv.find('='); if (eq == std::string::npos) { fprintf(stderr, "--opt name=value\n"); return 1; }
             lib_opts.push_back({kv.substr(0, eq), atoi(kv.substr(eq + 1).c_str())}); }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 1; }
@@ -148,12 +148,12 @@ int main(int argc, char** argv) {
     mb.mass = dev(mass); mb.evals = dev(evals); mb.evecs = dev(evecs);
     mb.g_rowptr = dev(rowptr); mb.g_col = dev(col); mb.g_vx = dev(vx); mb.g_vy = dev(vy);
     mb.gt_rowptr = dev(t_rowptr); mb.gt_col = dev(t_col); mb.gt_vx = dev(t_vx); mb.gt_vy = dev(t_vy);
-    int df_used = 0;
-    if (!no_plan && K == 128) {   // work plan of the one-launch diffusion operator, as diffusion_net.batch.MeshBatch attaches it
+    if (!no_plan && K == 128) {   // work plan of the direct back-projection, as diffusion_net.batch.MeshBatch attaches it
         const int nwg = L.sym<int (*)()>("dn_diffusion_plan_wgs")();
         std::vector<dn_tile_t> plan((size_t)DN_DIFFUSION_MAX_GROUPS * nwg);
-        df_used = L.sym<int (*)(const int32_t*, int, int, int, dn_tile_t*)>("dn_diffusion_plan")(sizes.data(), n_mesh, nwg, df_groups, plan.data());
-        if (df_used > 0) { plan.resize((size_t)df_used * nwg); mb.df_plan = dev(plan); mb.df_n_wg = nwg; mb.df_n_groups = df_used; mb.df_v_total = (int)V; }
+        if (L.sym<int (*)(const int32_t*, int, int, int, dn_tile_t*)>("dn_diffusion_plan")(sizes.data(), n_mesh, nwg, 0, plan.data()) > 0) {
+            mb.df_plan = dev(plan); mb.df_n_wg = nwg; mb.df_n_groups = 1; mb.df_v_total = (int)V;
+        }
     }
     {   // operand magnitudes for the split-fp16 engine, as diffusion_net.batch.MeshBatch provides them
         float am[2] = {0.f, 0.f};
@@ -234,7 +234,7 @@ int main(int argc, char** argv) {
     void* ws; HC(hipMalloc(&ws, wsb));
     hipStream_t st; HC(hipStreamCreate(&st));
     hipEvent_t e0, e1; HC(hipEventCreate(&e0)); HC(hipEventCreate(&e1));
-    printf("# lib=%s V=%lld meshes=%d K=%d C=%d tiles=%d chunks=%d (rows %d) nnz=%lld ws=%.0f MB diffusion-plan groups=%d wgs=%d spectral-gradient units=%d\n", libpath.c_str(), V, n_mesh, K, C, mb.n_tiles, mb.n_chunks, chunk_rows, nnz, wsb / 1e6, df_used, mb.df_n_wg, sg_units_n);
+    printf("# lib=%s V=%lld meshes=%d K=%d C=%d tiles=%d chunks=%d (rows %d) nnz=%lld ws=%.0f MB diffusion-plan wgs=%d spectral-gradient units=%d\n", libpath.c_str(), V, n_mesh, K, C, mb.n_tiles, mb.n_chunks, chunk_rows, nnz, wsb / 1e6, mb.df_n_wg, sg_units_n);
     auto df_wg_times = [&]() {   // -DDN_DF_TRACE builds: when did every workgroup of the last backproject_kernel start / end (10 ns ticks, chip-wide clock)
         auto rd = (int (*)(unsigned long long*, int))dlsym(L.h, "dn_debug_df_wg_times_read");
         if (!rd) return;
@@ -247,12 +247,6 @@ int main(int argc, char** argv) {
         auto pct = [](std::vector<double> v, double q) { std::sort(v.begin(), v.end()); return v[(size_t)(q * (v.size() - 1))]; };
         printf("  backproject workgroups (us from the first start): start min/median/max %.2f %.2f %.2f | end min/median/max %.2f %.2f %.2f | lifetime min/median/max %.2f %.2f %.2f\n",
                pct(st, 0), pct(st, .5), pct(st, 1), pct(en, 0), pct(en, .5), pct(en, 1), pct(life, 0), pct(life, .5), pct(life, 1));
-    };
-    auto df_trace = [&]() {   // libraries built with -DDN_DF_TRACE: s_memtime stamps of the first 16 workgroups of the one-launch diffusion kernel
-        auto rd = (int (*)(unsigned long long*, int))dlsym(L.h, "dn_debug_df_trace_read");
-        if (!rd) return;
-        std::vector<unsigned long long> tb(16 * 32); rd(tb.data(), 16 * 32);
-        for (int w = 0; w < 16; ++w) { printf("  wg %2d:", w); for (int i = 1; i < 24; ++i) printf(" %lld", tb[w * 32 + i] >= tb[w * 32] ? (long long)(tb[w * 32 + i] - tb[w * 32]) : -1ll); printf("\n"); }
     };
 
     auto timeit = [&](const char* name, double bytes, double flops, auto fn) {
@@ -361,7 +355,7 @@ int main(int argc, char** argv) {
             report(errs, refs); report(err, ref);
         }
         endl_();
-        if (trace) { DC(f(&mb, xr[0], tm, C, sv.xs, o0r[0], ws, wsb, st)); HC(hipStreamSynchronize(st)); df_trace(); df_wg_times(); }
+        if (trace) { DC(f(&mb, xr[0], tm, C, sv.xs, o0r[0], ws, wsb, st)); HC(hipStreamSynchronize(st)); df_wg_times(); }
     }
     if (want("diffusion_bwd")) {   // needs sv.xs of the forward above (run --ops diffusion,diffusion_bwd for the check)
         auto f = L.sym<int (*)(const dn_mesh_batch_t*, const float*, const float*, const float*, int, const float*, float*, float*, void*, size_t, void*)>("dn_diffusion_bwd_f32");
@@ -391,7 +385,7 @@ int main(int argc, char** argv) {
             report(err, ref); report(errt, reft);
         }
         endl_();
-        if (trace) { DC(f(&mb, yr[0], sv.xs, tm, C, xr[0], o1r[0], dt, ws, wsb, st)); HC(hipStreamSynchronize(st)); df_trace(); }
+        if (trace) { DC(f(&mb, yr[0], sv.xs, tm, C, xr[0], o1r[0], dt, ws, wsb, st)); HC(hipStreamSynchronize(st)); }
     }
     if (want("spmm")) {
         auto f = L.sym<int (*)(const dn_mesh_batch_t*, const float*, int, float*, float*, void*)>("dn_grad_apply_fwd_f32");

@@ -33,8 +33,6 @@ def family(name):
         return "tngemm_kernel"
     if "backproject_kernel" in name:
         return "backproject_kernel"
-    if "diffuse_kernel" in name:
-        return "diffuse_kernel"
     if "spmm_kernel" in name:
         return "spmm_kernel"
     if "chain_fwd_kernel" in name:
