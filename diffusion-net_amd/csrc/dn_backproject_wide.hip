@@ -18,9 +18,9 @@
 #include "dn_chain_tiles.h"
 #include "dn_direct_tiles.h"
 
-#ifndef DN_BW_G
-#define DN_BW_G 1        // 16-row groups per wave.  2 (four waves per workgroup, one per SIMD, accumulators in AGPRs, every spectrum fragment read from LDS
-#endif                   // feeds two row groups: half the LDS traffic) measured the same on MI355X (458-472 vs 459-469 us for the whole operator): not LDS-bound
+// 16-row groups per wave.  2 (four waves per workgroup, one per SIMD, accumulators in AGPRs, every spectrum fragment read from LDS feeds two
+// row groups: half the LDS traffic) measured the same on MI355X (458-472 vs 459-469 us for the whole operator): not LDS-bound
+constexpr int DN_BW_G = 1;
 
 #define DN_BW_RING 3
 #define DN_BW_MAXP 128   // tiles per workgroup (their descriptors live in LDS; the launcher checks)

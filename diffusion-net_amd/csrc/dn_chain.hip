@@ -29,40 +29,13 @@
 
 #include "dn_chain_tiles.h"
 
-#ifndef DN_CH_GCR
-#define DN_CH_GCR 1      // (1: 393.9 us block forward at 16 x 10k, 2: 408.1, 3: 431.5 -- registers, not bytes in flight; profiles/r05_rcg_ab.txt)
-#endif
-#ifndef DN_CH_L0_EXACT
-#define DN_CH_L0_EXACT 1  // layer 0's x / xd row requests behind the piece request and counted exactly in the end-of-piece wait (0: the round-4 order; A/B)
-#endif
-#ifndef DN_CH_PF_WIDE
-#define DN_CH_PF_WIDE 2
-#endif
-#ifndef DN_CH_NXR_WIDE
-#define DN_CH_NXR_WIDE 5  // x / xd operand rows of layer 0 in flight, in pieces + 1, in the C = 256 form (3 at C <= 128)
-#endif
-#ifndef DN_CH_GCR_WIDE
-#define DN_CH_GCR_WIDE 2 // the same in the C = 256 form (one wave per SIMD: 16 KiB in flight per wave)
-#endif
-#ifndef DN_CH_LINES_WIDE
-#define DN_CH_LINES_WIDE 1   // C = 256: the result rows as whole-line stores too (dn_chain_tiles.h, ch_st_tiles)
-#endif
-#ifndef DN_CH_ROLL
-#define DN_CH_ROLL 1     // rolling row requests in the row-contiguous gather: 1 = in the C = 256 form (latency-bound there: one wave per SIMD), 2 = everywhere
-                         // (C = 128: 28 spilled registers in the benchmark's kernel), 0 = all rows of a step requested, then all summed
-#endif
-#ifndef DN_CH_SG_PF
-#define DN_CH_SG_PF 0    // contraction steps of the spectral stage whose operand fragments are requested a pass ahead (24 registers each: 1 / 2 / 3 / 4 steps carried cost 10 / 42 / 101 / 140 spilled registers at C = 128 wherever they are requested)
-#endif
-#ifndef DN_CH_SG_PFPOINT
-#define DN_CH_SG_PFPOINT 1
-#endif
-#ifndef DN_CH_SG_MAXP
-#define DN_CH_SG_MAXP 64 // passes per workgroup of the spectral-gradient form (their descriptors live in LDS; the launcher checks)
-#endif
-#ifndef DN_CH_RCG
-#define DN_CH_RCG 1      // row-contiguous gather in the one-half-per-wave form of the chained forward (0: operand-layout gather everywhere; A/B)
-#endif
+// Measured constants of the chained forward (the alternatives that lost: tools/experiments/build_switches/README.md)
+constexpr int DN_CH_GCHUNK = 4;    // pattern entries gathered per step of the operand-layout gather (all their row pieces in flight together)
+constexpr int DN_CH_GCR = 1;       // pattern entries per gather step of the row-contiguous form (1: 393.9 us block forward at 16 x 10k, 2: 408.1, 3: 431.5 -- registers, not bytes in flight; profiles/r05_rcg_ab.txt)
+constexpr int DN_CH_GCR_WIDE = 2;  // the same in the C = 256 form (one wave per SIMD: 16 KiB in flight per wave)
+constexpr int DN_CH_PF_WIDE = 2;   // weight-fragment prefetch distance of the C = 256 form, in tile pairs
+constexpr int DN_CH_NXR_WIDE = 5;  // x / xd operand rows of layer 0 in flight, in pieces + 1, in the C = 256 form (3 at C <= 128)
+constexpr int DN_CH_SG_MAXP = 64;  // passes per workgroup of the spectral-gradient form (their descriptors live in LDS; the launcher checks)
 
 template <int C>
 __global__ __launch_bounds__(1024) void chain_prep_kernel(ChainPrepArgs a) {
@@ -183,7 +156,7 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
     float* sbias = reinterpret_cast<float*>(ring + RING * PIECE);          // [DN_CH_LAYERS][C]  (G0: not staged, the epilogues read the biases from memory)
     // row-contiguous gather (RCG; at C = 128 in the one-half-per-wave form only: it needs the registers the second half's features occupy
     // otherwise.  The C = 256 form runs one wave per SIMD with 512 registers and takes it with both halves)
-    constexpr bool RCG = !SG && (HH == 1 || C >= 256) && DN_CH_RCG != 0;
+    constexpr bool RCG = !SG && (HH == 1 || C >= 256);
     constexpr int GC = G0 ? 128 : C;      // channels per gather sweep (G0: the row in two column halves -- sums, request buffers and the slice are
                                           // those of C = 128, the half gathered first is in its final registers while the second one runs)
     constexpr int NSW = C / GC;           // sweeps
@@ -330,26 +303,21 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
     for (int j = 0; j < DN_CH_LAYERS; ++j) hmax[j] = 0.f;
     float omax = 0.f;
     // SG: the operand fragments of a pass -- [Phi | G_X Phi | G_Y Phi] of this wave's 16 rows, pre-split fp16 (hi, lo), this lane's eight
-    // contraction slots of step T as one uint4 per plane (every request of the wave is 1 KiB contiguous) -- are requested a pass AHEAD, inside
-    // the previous pass's layer 0, and carried in registers to the top of their pass
+    // contraction slots of step T as one uint4 per plane (every request of the wave is 1 KiB contiguous) -- are all requested at the top of their
+    // pass and arrive under the first steps' products (carried from the previous pass they cost 10 .. 140 spilled registers at C = 128)
     [[maybe_unused]] uint4 fr[SG ? KE : 1][3][2];
-    // (all KE steps carried across the pass cost 140 spilled registers -- the fragments went to scratch as they arrived; the first PFK steps are
-    // carried, the rest are requested at the top of their pass and arrive under the first steps' products)
-    constexpr int PFK = SG ? (DN_CH_SG_PF < KE ? DN_CH_SG_PF : KE) : 0;
-    auto load_frags = [&](const int grp, const int t0, const int t1) {
+    auto load_frags = [&](const int grp) {
         if constexpr (SG) {
             const uint4* fp = a.sg_pack + (size_t)grp * (3 * KE * 128) + lane;
 #pragma unroll
             for (int T = 0; T < KE; ++T)
 #pragma unroll
-                for (int op = 0; op < 3; ++op)
-                    if (T >= t0 && T < t1) {
-                        fr[T][op][0] = fp[(size_t)(op * KE + T) * 128];
-                        fr[T][op][1] = fp[(size_t)(op * KE + T) * 128 + 64];
-                    }
+                for (int op = 0; op < 3; ++op) {
+                    fr[T][op][0] = fp[(size_t)(op * KE + T) * 128];
+                    fr[T][op][1] = fp[(size_t)(op * KE + T) * 128 + 64];
+                }
         }
     };
-    if constexpr (SG) load_frags(ch_uniform_i(pinfo[0].w) + wave, 0, PFK);
 
     for (int pass = 0; pass < npass; ++pass) {
         CH_TR();
@@ -357,7 +325,7 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
         int rb = unit * (16 * HH * NW) + 16 * HH * wave;     // first of this wave's 32 rows (row * C fits 32 bits for every batch the library takes)
         int row_end = a.V;
         [[maybe_unused]] float u_xd = 1.f, u_gx = 1.f, u_gy = 1.f;
-        [[maybe_unused]] int grp_nx = 0, grp_cur = 0;
+        [[maybe_unused]] int grp_cur = 0;
         if constexpr (SG) {
             // this pass's rows (of one mesh; past the mesh's end the packed operands hold zeros) and the next pass's mesh and group, which the piece
             // requests and the operand requests that run ahead need
@@ -367,7 +335,6 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
             rb = ch_uniform_i(pi_.x) + 16 * HH * wave;
             row_end = ch_uniform_i(pi_.y);
             mesh_nx = ch_uniform_i(pn_.z);
-            grp_nx = ch_uniform_i(pn_.w) + HH * wave;
             grp_cur = ch_uniform_i(pi_.w) + HH * wave;
             u_xd = ch_uniform(ps_.x); u_gx = ch_uniform(ps_.y); u_gy = ch_uniform(ps_.z);
         }
@@ -437,8 +404,7 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
                     // ---- [xd | gx | gy] = [Phi | G_X Phi | G_Y Phi][16 rows] ys[mesh]: the operand fragments arrive pre-split (fp16 hi / lo, this
                     // lane's eight contraction slots of step T as one uint4 per plane: every request of the wave is 1 KiB contiguous), all of a pass's
                     // requested up front; the spectrum's pieces come through the ring.  One piece read from LDS feeds all three products.
-                    // (fr: steps 0 .. PFK - 1 requested a pass ahead, in front of the previous pass's hidden layers -- before the loop for the first pass)
-                    load_frags(grp_cur, PFK, KE);
+                    load_frags(grp_cur);
                     CH_TR();
                     dn_f32x4 sa[3][NT];
 #pragma unroll
@@ -568,7 +534,7 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
                         };
                         // (two row buffers -- the rows of step k + 1 requested before the sums of step k are formed -- were measured: 85 spilled
                         // registers, block forward 471 vs 410 us; profiles/r05_rcg_ab.txt)
-                        if constexpr (DN_CH_ROLL == 2 || (DN_CH_ROLL == 1 && G0)) {
+                        if constexpr (G0) {
                             // Rolling form, same registers: row group i of step k is summed as soon as ITS request has landed (requests return in
                             // order: the other NI - 1 stay in flight) and its buffer is re-requested for step k + 1 at once -- NI requests in flight
                             // all the time instead of a sawtooth between NI and none.  The pattern entries run two steps ahead.
@@ -772,12 +738,7 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
                     if (SG && !G0 && pi >= NK) ch_split8(xdv[(2 * (pi - NK)) % NT], xdv[(2 * (pi - NK) + 1) % NT], s_in, fh[hh], fl[hh]);
                     else ch_split8(nx[pi % NXR][hh][0], nx[pi % NXR][hh][1], s_in, fh[hh], fl[hh]);
                 }
-                if constexpr (DN_CH_L0_EXACT == 0) {
-                    if (pi + NXR - 1 < NFETCH) fetch(pi + NXR - 1, nx[(pi + NXR - 1) % NXR]);
-                    CH_PIECE_BEGIN();
-                    CH_MMA2(acc, fh[0], fl[0], fh[HH - 1], fl[HH - 1]);
-                    CH_PIECE_END();
-                } else {
+                {
                     // The row requests go out BEHIND the piece request of their piece, and the wait at the end of the piece counts them: the
                     // operations younger than the piece it needs are two piece requests and the row requests of this piece and the two before
                     // it (2 HH each) -- none of them has to land.  (With the rows requested first and a wait of two pieces flat, every piece
@@ -803,10 +764,6 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
         CH_TR();
         // =================================================== hidden layers: h_j = dropout(relu(acc + b_j)) -> operand fragments -> next product
         //      (layers.py:143-160: the dropout in front of linear layer j + 1 is applied where h_j is produced)
-        // SG: the next pass's operand fragments go out here -- layer 0's operands are dead, the hidden layers hold two 32-register sets -- and
-        // have the rest of the pass to arrive (requested inside layer 0 they cost 140 spilled registers)
-        const bool pf = SG && pass + 1 < npass;
-        if constexpr (SG && DN_CH_SG_PFPOINT == 0) { if (pf) load_frags(grp_nx, 0, PFK); }
         float s_act = s_in;               // scale the operand of the product just finished was split with
         uint4 hfh[HH][NK], hfl[HH][NK];     // hidden activations as operand fragments
 #pragma unroll 1
@@ -941,17 +898,12 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
             for (int T = 0; T < NK; ++T) {
                 CH_PIECE_BEGIN();
                 CH_MMA2(acc, hfh[0][T], hfl[0][T], hfh[HH - 1][T], hfl[HH - 1][T]);
-                // (SG: the 6 KE fragment requests issued in front of this loop are younger than the piece waited for -- DMA(gp + 1), out RING - 2
-                // pieces ago -- during its first RING - 2 pieces: they may stay in flight; loads only are counted)
-                if (SG && DN_CH_SG_PFPOINT == 0 && T < RING - 2 && j == 0 && pf) { CH_WAIT_OPS((RING - 2) * LPT + 6 * PFK); CH_BARRIER(); ++gp; }
-                else CH_PIECE_END();
+                CH_PIECE_END();
             }
             CH_TR();
         }
         // =================================================== last layer: out = acc + b + x   (layers.py:236-239)
         {
-            // SG, DN_CH_SG_PFPOINT = 1: the next pass's operand fragments go out in front of the last epilogue (the hidden fragments are dead)
-            if constexpr (SG && DN_CH_SG_PFPOINT == 1) { if (pf) load_frags(grp_nx, 0, PFK); }
             const int jl = a.n_mlp - 1;
             const float so = ch_pow2_inv(s_act) * (jl == 1 ? sw_inv[1] : (jl == 2 ? sw_inv[2] : sw_inv[3]));
             const float* bj = G0 ? (jl == 1 ? a.bias[1] : (jl == 2 ? a.bias[2] : a.bias[3])) + 4 * q : sbias + jl * C + 4 * q;
@@ -961,12 +913,9 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
 #pragma unroll
                 for (int hh = 0; hh < HH; ++hh) {
                     const float* px = a.x + (long long)rch[hh] * C + 4 * q;
-                    float* oo = a.out + (long long)rowh[hh] * C + 4 * q;
                     float4 r[NT];
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) r[nt] = *reinterpret_cast<const float4*>(px + 16 * nt);
-#if DN_CH_LINES_WIDE
-                    (void)oo;
                     ch_st_tiles<NT, true>(a.out, C, rowh[hh], row_end, m, q, [&](const int nt) {
                         float4 y;
                         y.x = acc[hh][nt][0] * so + r[nt].x;
@@ -975,18 +924,6 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
                         y.w = acc[hh][nt][3] * so + r[nt].w;
                         omax = dn_f4_amax(omax, y);
                         return y; });
-#else
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        float4 y;
-                        y.x = acc[hh][nt][0] * so + r[nt].x;
-                        y.y = acc[hh][nt][1] * so + r[nt].y;
-                        y.z = acc[hh][nt][2] * so + r[nt].z;
-                        y.w = acc[hh][nt][3] * so + r[nt].w;
-                        omax = dn_f4_amax(omax, y);
-                        if (liveh[hh]) ch_st4(oo + 16 * nt, y);
-                    }
-#endif
                 }
             } else {
                 float4 r4[HH][NT];

@@ -51,14 +51,11 @@ __device__ __forceinline__ float ch_tanh(float x) {
 // a b + c d with the roundings spelled out: one product rounded, the other fused into the sum.  Left to the compiler's contraction the choice of
 // WHICH product is fused follows the surrounding code (a restructure of the kernel flipped it and moved the tanh features by one ulp in a
 // quarter of the elements -- 4.6e-6 -> 6.3e-6 from fp64 on the trained-checkpoint golden after four blocks); written out, it stays put.
-#ifndef DN_CH_DOT_ORDER
-#define DN_CH_DOT_ORDER 0
-#endif
 __device__ __forceinline__ float ch_dot2(float a, float b, float c, float d) {
 #ifdef DN_EMULATE
     return a * b + c * d;
 #else
-    return DN_CH_DOT_ORDER ? __builtin_fmaf(c, d, __fmul_rn(a, b)) : __builtin_fmaf(a, b, __fmul_rn(c, d));
+    return __builtin_fmaf(a, b, __fmul_rn(c, d));
 #endif
 }
 // 1 / s for a power of two s = 2^k, -126 <= k <= 126 (what dn_pow2_scale returns but for its two clamped extremes): exponent arithmetic, exact
@@ -82,17 +79,8 @@ __device__ __forceinline__ int ch_uniform_i(int v) {
 #endif
 }
 // Streaming global accesses of the chained kernels (dn_common.h): every activation tile is written exactly once per launch and consumed by
-// a LATER kernel.  Build with -DDN_CH_STREAM=0 for plain stores (A/B).
-#ifndef DN_CH_STREAM
-#define DN_CH_STREAM 1
-#endif
-__device__ __forceinline__ void ch_st4(float* p, const float4 v) {
-#if DN_CH_STREAM
-    dn_st4_stream(p, v);
-#else
-    *reinterpret_cast<float4*>(p) = v;
-#endif
-}
+// a LATER kernel.
+__device__ __forceinline__ void ch_st4(float* p, const float4 v) { dn_st4_stream(p, v); }
 // ---- whole-line stores of accumulator-layout tiles.  Lane (m, q) of a wave holds channels 16 nt + 4 q .. + 3 of row m: a store of tile nt
 // writes 64 contiguous bytes per row -- half a 128-byte line; the other half comes with the store of tile nt + 1.  As streaming stores
 // those halves reach memory separately often enough to cost 19-27 % more written bytes than the arrays hold (WRITE_SIZE of the chained
@@ -100,9 +88,6 @@ __device__ __forceinline__ void ch_st4(float* p, const float4 v) {
 // profiles/r06_line_stores.txt).  Here the two tiles are exchanged between rows m and m + 8 (DPP row_ror:8: one v_mov per register) so
 // that ONE instruction writes tiles nt, nt + 1 of rows 0..7 and the next one of rows 8..15: every row segment written by an
 // instruction is a whole line.  base: the array; row: this lane's row; v_end: rows below it exist.
-#ifndef DN_CH_LINES
-#define DN_CH_LINES 1
-#endif
 __device__ __forceinline__ float ch_rot8(float v) {      // the value lane (m + 8) % 16 of the same 16-lane row holds
 #ifdef DN_EMULATE
     const int l_ = (int)(threadIdx.x & 63);
@@ -115,7 +100,7 @@ __device__ __forceinline__ float ch_rot8(float v) {      // the value lane (m + 
 // LINES = false: the plain form, one 64-byte segment per row and instruction (kernels at the register limit: the exchange costs ~16 registers)
 template <int NT, bool LINES = true, typename F>
 __device__ __forceinline__ void ch_st_tiles(float* base, const int C, const long long row, const int v_end, const int m, const int q, F&& tile) {
-  if constexpr (LINES && DN_CH_LINES != 0) {
+  if constexpr (LINES) {
     static_assert(NT % 2 == 0, "tile pairs");
     const bool hi = m >= 8;
     const long long r0 = hi ? row - 8 : row, r1 = hi ? row : row + 8;      // rows this lane writes in the first / second instruction of a pair
@@ -139,17 +124,8 @@ __device__ __forceinline__ void ch_st_tiles(float* base, const int C, const long
   }
 }
 // (the LOADS of the backward's single-use tiles are plain since round 6: a 64-byte request per row is half a line, the other half comes with the next
-// tile's request, and a streaming line is often gone by then -- FETCH_SIZE 387 -> 375 k KiB, block backward 851-858 -> 842-846 us; -DDN_CH_STREAM_LD=1: A/B)
-#ifndef DN_CH_STREAM_LD
-#define DN_CH_STREAM_LD 0
-#endif
-__device__ __forceinline__ float4 ch_ld4(const float* p) {
-#if DN_CH_STREAM_LD
-    return dn_ld4_stream(p);
-#else
-    return *reinterpret_cast<const float4*>(p);
-#endif
-}
+// tile's request, and a streaming line is often gone by then -- FETCH_SIZE 387 -> 375 k KiB, block backward 851-858 -> 842-846 us)
+__device__ __forceinline__ float4 ch_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // int shuffle (the emulator's shuffles carry floats: row indices of its test meshes are exact in fp32)
 __device__ __forceinline__ int ch_shfl_i(int v, int src_lane) {
 #ifdef DN_EMULATE
@@ -196,12 +172,7 @@ __device__ __forceinline__ float ch_wave_max(float m) {
 #endif
 }
 
-#ifndef DN_CH_RING
 #define DN_CH_RING 4      // LDS slots of the piece stream; DN_CH_RING - 1 pieces are requested ahead of the one being multiplied
-#endif
-#ifndef DN_CH_GCHUNK
-#define DN_CH_GCHUNK 4    // pattern entries gathered per step (all their row pieces in flight together)
-#endif
 // One LDS-DMA request: 16 bytes per lane, global -> LDS, lane l's data lands at lds_byte + 16 l (lds_byte wave-uniform).  Inline asm on
 // purpose: the compiler's waitcnt bookkeeping does not see it, so it neither drains the request queue at a barrier nor at the next use of
 // an ordinary load while requests are in flight; the kernel counts them itself (CH_WAIT_PIECES).  Loads return in order, so a compiler-made

@@ -184,68 +184,12 @@ __device__ __forceinline__ void dn_st4_stream(float* p, const float4 v) {
     *reinterpret_cast<float4*>(p) = v;
 #endif
 }
-__device__ __forceinline__ float4 dn_ld4_stream(const float* p) {
-#ifndef DN_EMULATE
-    const dn_v4f t = __builtin_nontemporal_load(reinterpret_cast<const dn_v4f*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-#else
-    return *reinterpret_cast<const float4*>(p);
-#endif
-}
-// streaming (nontemporal) 16-byte accesses: the hand-written copy runs at 6.2-6.4 TB/s with them against 5.2-5.9 TB/s without (tools/kbench copyk);
-// in the row GEMM they moved the block by +-2 % either way (round 3, tools/experiments/rowgemm_ws_knobs/) and are not used there.
-typedef float dn_vf4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void dn_store_f4_nt(float* p, const float4& v) {
-#ifdef DN_EMULATE
-    *reinterpret_cast<float4*>(p) = v;
-#else
-    __builtin_nontemporal_store(dn_vf4{v.x, v.y, v.z, v.w}, reinterpret_cast<dn_vf4*>(p));
-#endif
-}
-__device__ __forceinline__ float4 dn_load_f4_nt(const float* p) {
-#ifdef DN_EMULATE
-    return *reinterpret_cast<const float4*>(p);
-#else
-    const dn_vf4 v = __builtin_nontemporal_load(reinterpret_cast<const dn_vf4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#endif
-}
-// L1-bypassing ("sc1") 8-byte loads: agent-scope relaxed atomics.  What a workgroup reads of another workgroup's write-through (sc1)
-// stores inside ONE launch: MI355X_MICROARCH.md, inter-workgroup visibility -- "sc1 loads may replace the acquire only
-// when the producer stored sc1".  Compiler-tracked (no inline asm: an asm load's destination may be spilled before the data arrives).
-__device__ __forceinline__ float2 dn_ld2_coherent(const float* p) {
-#ifdef DN_EMULATE
-    return *reinterpret_cast<const float2*>(p);
-#else
-    const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float2(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32)));
-#endif
-}
-__device__ __forceinline__ float4 dn_ld4_coherent(const float* p) {
-    const float2 lo = dn_ld2_coherent(p), hi = dn_ld2_coherent(p + 2);
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-}
 // Plain multiplies on purpose.  An explicit two-element vector multiply here (v_pk_mul_f32 with a broadcast operand in src1,
 // `op_sel_hi:[1,0]`) produced INTERMITTENTLY wrong low halves on gfx950 / ROCm 7.2: one stale bf16 pair in a few launches per
 // thousand at small sizes, in every launch at the benchmark size -- a whole output column of a tile off by ~1e-1 relative, found
-// by tools/determinism_stress.py, invisible to the 2e-4 gradient tolerance.  -DDN_F4_PACKED restores that form for re-testing;
-// the packed forms the compiler's SLP pass emits from the code below were bitwise stable in the same stress runs.
-__device__ __forceinline__ float4 dn_f4_mul(float4 a, float4 b) {
-#if defined(DN_F4_PACKED) && !defined(DN_EMULATE)   // experiment switch: explicit two-element vector multiplies
-    typedef float dn_f2 __attribute__((ext_vector_type(2)));
-    const dn_f2 lo = dn_f2{a.x, a.y} * dn_f2{b.x, b.y}, hi = dn_f2{a.z, a.w} * dn_f2{b.z, b.w};
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-#else
-    return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
-#endif
-}
-__device__ __forceinline__ float4 dn_f4_scale(float4 a, float s) {
-#if defined(DN_F4_PACKED) && !defined(DN_EMULATE)
-    return dn_f4_mul(a, make_float4(s, s, s, s));
-#else
-    return make_float4(a.x * s, a.y * s, a.z * s, a.w * s);
-#endif
-}
+// by tools/determinism_stress.py, invisible to the 2e-4 gradient tolerance.  Never write that form here again.
+__device__ __forceinline__ float4 dn_f4_mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+__device__ __forceinline__ float4 dn_f4_scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 __device__ __forceinline__ float dn_f4_get(const float4& v, int t) {
     return t == 0 ? v.x : (t == 1 ? v.y : (t == 2 ? v.z : v.w));
 }
@@ -313,10 +257,6 @@ __device__ __forceinline__ void dn_amax_commit_group(float* word, float m, unsig
             if (mm > 0.f && mm > *reinterpret_cast<volatile float*>(word)) atomicMax(reinterpret_cast<unsigned*>(word), __float_as_uint(mm));
         }
     }
-}
-// per-lane form for kernels whose lanes do not all reach the end together: skip the atomic unless this lane would raise the word
-__device__ __forceinline__ void dn_amax_commit_lane(float* word, float m) {
-    if (m > *reinterpret_cast<volatile float*>(word)) atomicMax(reinterpret_cast<unsigned*>(word), __float_as_uint(m));
 }
 __device__ __forceinline__ float dn_f4_amax(float m, const float4& v) {
     const float a = fabsf(v.x) > fabsf(v.y) ? fabsf(v.x) : fabsf(v.y), b = fabsf(v.z) > fabsf(v.w) ? fabsf(v.z) : fabsf(v.w);
@@ -427,9 +367,7 @@ static inline int dn_num_cus() {
 // number of partial results a tngemm launch over `nchunks` chunks with grouping `group` writes
 static inline int dn_tn_npartial(int nchunks, int group) { return (nchunks + (group < 1 ? 1 : group) - 1) / (group < 1 ? 1 : group); }
 // grouping for sums over ALL rows (weight gradients): about two workgroups per CU
-#ifndef DN_TN_TARGET_PARTIALS
-#define DN_TN_TARGET_PARTIALS 512   // about two (lock-step) workgroups per CU (a wave-specialised one-per-CU kernel was measured and rejected: tools/experiments/tngemm_ws/)
-#endif
+constexpr int DN_TN_TARGET_PARTIALS = 512;   // about two (lock-step) workgroups per CU (a wave-specialised one-per-CU kernel was measured and rejected: tools/experiments/tngemm_ws/)
 static inline int dn_tn_global_group(int nchunks) { int g = (nchunks + DN_TN_TARGET_PARTIALS - 1) / DN_TN_TARGET_PARTIALS; return g < 1 ? 1 : g; }
 // the same for an M x N result of several 128 x 128 output tiles: every (partial, tile) pair is a workgroup, so the partial count --
 // and with it the partial-result traffic, 2 x 4 M N bytes each -- shrinks with the tile count (never below 128 partials; never

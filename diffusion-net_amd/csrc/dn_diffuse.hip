@@ -56,7 +56,7 @@ __global__ __launch_bounds__(DN_TX_THREADS) DN_WAVES_PER_EU(2) void backproject_
         // for the forward operator, 115.7 vs 116.7 backward (profiles/r05_backproject_ab.txt; streaming stores / loads measured too: slower)
         RdStart st;
         rd_rows_begin(a.evecs, K, me.row0, me.row0 + me.nrows, wave, lane, st);
-        rd_stage_b_nn<DN_TX_THREADS, false, NP>(a.ys + (long long)me.mesh * K * C, C, smem, tid, sb);
+        rd_stage_b_nn<DN_TX_THREADS, NP>(a.ys + (long long)me.mesh * K * C, C, smem, tid, sb);
         __syncthreads();
         RgArgs rg;
         rg.o0 = a.out; rg.ldo = C; rg.ldr = C; rg.N = C; rg.r0 = a.add; rg.rowv = a.rowv; rg.bias = nullptr; rg.mask = nullptr; rg.rng_seed = 0ull;

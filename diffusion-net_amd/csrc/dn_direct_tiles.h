@@ -60,8 +60,7 @@ __device__ __forceinline__ int rd_k0(int s, int lg, int h) { return 32 * s + 16 
 
 // Split a 128 x 128 operand B[k][n] (row-major, n contiguous, leading dimension ldb) into the fragment-ordered planes: a thread
 // fetches an 8 (k) x 4 (n) block as eight float4 along n -- the eight k of four items (four consecutive lanes).  NTHR threads.
-// COH: B was written by other workgroups of the SAME launch (write-through stores): L1-bypassing loads.
-template <int NTHR, bool COH = false, int NP = 3>
+template <int NTHR, int NP = 3>
 __device__ __forceinline__ void rd_stage_b_nn(const float* bp, int ldb, unsigned char* sB, int tid, float sc = 1.f) {
 #pragma unroll
     for (int h = 0; h < 512 / NTHR; ++h) {                     // 4 steps x 4 lane groups x 32 column quads = 512 blocks
@@ -73,8 +72,8 @@ __device__ __forceinline__ void rd_stage_b_nn(const float* bp, int ldb, unsigned
         for (int j = 0; j < 4; ++j) {
             const float* p0 = cp + (long long)(rd_k0(s, lg, 0) + j) * ldb;
             const float* p1 = cp + (long long)(rd_k0(s, lg, 1) + j) * ldb;
-            r[j] = COH ? dn_ld4_coherent(p0) : *reinterpret_cast<const float4*>(p0);
-            r[4 + j] = COH ? dn_ld4_coherent(p1) : *reinterpret_cast<const float4*>(p1);
+            r[j] = *reinterpret_cast<const float4*>(p0);
+            r[4 + j] = *reinterpret_cast<const float4*>(p1);
         }
         const int t = nq >> 2;                                   // 16-column tile of columns 4 nq .. 4 nq + 3
 #pragma unroll

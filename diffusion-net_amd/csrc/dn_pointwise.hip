@@ -646,9 +646,7 @@ int dn_launch_smallk_rows(const float* x, int K, const float* W, int w_kn, const
     long long nb = (rows + rpp - 1) / rpp;
     // every workgroup ends with one atomic on the magnitude word, and in a kernel this short they all arrive together (the check-first
     // read sees the word unraised): the atomics of one address retire at ~8 ns each -- measured at 160 k rows: 46 / 32 / 28 us with 4096 / 1024 / 512 workgroups
-#ifndef DN_SMALLK_MAX_WGS
-#define DN_SMALLK_MAX_WGS 512
-#endif
+    constexpr int DN_SMALLK_MAX_WGS = 512;
     if (nb > DN_SMALLK_MAX_WGS) nb = DN_SMALLK_MAX_WGS;
     dn_prof_begin(DN_K_SMALL, stream);
     if (K <= 4) {

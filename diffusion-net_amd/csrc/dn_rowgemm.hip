@@ -9,13 +9,6 @@
 // implemented in dn_rowgemm_persist.hip: launches a persistent kernel if the product is eligible (returns true) ...
 bool dn_rowgemm_try_persistent(const RgArgs& g, int ntiles, int nout, hipStream_t stream, int* err);
 
-#ifndef DN_RG_X3
-#define DN_RG_X3 1   // -DDN_RG_X3=0: exact-f32 MFMA in the two-output kernels
-#endif
-#if defined(DN_DEBUG_SCALES) && !defined(DN_EMULATE)   // development build: the operand scales every workgroup of the two-output split-fp16 kernel read
-__device__ float dn_dbg_scales[2 * 8192];
-extern "C" int dn_debug_scales_read(float* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dn_dbg_scales), (size_t)(n < 2 * 8192 ? n : 2 * 8192) * sizeof(float)); }
-#endif
 #define RG_STORE(buf)                                                                                                          \
     do {                                                                                                                       \
         if constexpr (X3) rg_store_x3<NTHR, NOUT, BCOLK, HASQ, A_IT, B_IT, NP>(reinterpret_cast<unsigned char*>(buf),           \
@@ -29,13 +22,6 @@ extern "C" int dn_debug_scales_read(float* out, int n) { return (int)hipMemcpyFr
                                                       wc * NT * 32, li, ls, acc);                                              \
         else rg_compute<TN, MT, NT, NOUT, BCOLK>((buf), (buf) + SA, wr * MT * 32, wc * NT * 32, li, ls, acc);                  \
     } while (0)
-#ifndef DN_RG2_VEC_EPI
-#define DN_RG2_VEC_EPI 1   // parked float4 epilogue of the two-output split-bf16 kernel (0: per-element dword epilogue)
-#endif
-#ifndef DN_RG2_EARLY_EPI
-#define DN_RG2_EARLY_EPI(MODE) 1   // epilogue operands fetched under the last two slices (measured: fwd 201 -> 186 us, bwd pair 360 -> 348 us; 0: after them)
-#endif
-constexpr bool rg_is_x3(int TN, int NTHR, int NOUT, bool ALIGNED) { return DN_RG_X3 && ALIGNED && NOUT == 2 && TN == 128 && NTHR == 512; }
 // NP: planes of the split engine on the two-output path (3 = split-bf16; 2 = split-fp16 with the operand scales of RgArgs.a_amax / b_amax)
 template <int TN, int WR, int WC, int NOUT, int MODE, bool ALIGNED, bool BCOLK, int NP = 3>
 __global__ __launch_bounds__(WR* WC * 64) DN_MIN_WAVES_PER_EU(1)
@@ -46,9 +32,6 @@ void rowgemm_kernel(RgArgs g) {
         sa = dn_pow2_scale(dn_amax_eval(g.a_amax));
         sb = dn_pow2_scale(dn_amax_eval(g.b_amax));
         so = (1.f / sa) * (1.f / sb);
-#if defined(DN_DEBUG_SCALES) && !defined(DN_EMULATE)
-        if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.y == 0) { dn_dbg_scales[2 * blockIdx.x] = sa; dn_dbg_scales[2 * blockIdx.x + 1] = sb; }
-#endif
     }
 
     constexpr int NTHR = WR * WC * 64;
@@ -56,8 +39,8 @@ void rowgemm_kernel(RgArgs g) {
     constexpr int NT = TN / (32 * WC);
     constexpr int A_IT = DN_TM * 8 / NTHR;
     constexpr int B_IT = DN_KB * TN / 4 / NTHR;
-    // the two-output (gradient feature) products run on split-bf16 MFMA: three bf16 planes per operand tile
-    constexpr bool X3 = DN_RG_X3 && ALIGNED && NOUT == 2 && TN == 128 && NTHR == 512;
+    // the aligned two-output (gradient feature) products run on split-bf16 MFMA: three bf16 planes per operand tile (unaligned: exact f32)
+    constexpr bool X3 = ALIGNED && NOUT == 2 && TN == 128 && NTHR == 512;
     constexpr int SA = X3 ? (DN_TM * 64 * 3) / 4 : DN_TM * DN_KB;                     // floats of one A slice
     constexpr int SBUF = SA + NOUT * (X3 ? (128 * 64 * 3) / 4 : DN_KB * TN);          // one (A,B) slice buffer; two in LDS
     constexpr bool HASQ = (MODE == DN_EPI_GRADFEAT_BWD);   // the only op whose A operand is an elementwise product
@@ -90,8 +73,9 @@ void rowgemm_kernel(RgArgs g) {
     for (int s = 0; s < g.nseg; ++s) nslices += (g.a[s].w + DN_KB - 1) / DN_KB;
 
     // Two-output split-bf16 configuration: the epilogue's elementwise operands (float4 pieces, see below) are fetched while the last
-    // two slices are still being multiplied -- with one workgroup per CU nothing else would cover that HBM round trip.
-    constexpr bool VEPI = X3 && DN_RG2_VEC_EPI;
+    // two slices are still being multiplied -- with one workgroup per CU nothing else would cover that HBM round trip
+    // (measured: fwd 201 -> 186 us, bwd pair 360 -> 348 us against a fetch after them).
+    constexpr bool VEPI = X3;
     constexpr int NPC = VEPI ? 128 * 128 / 4 / NTHR : 1;   // 8 pieces per thread
     float4 er0[NPC], er1[NPC], er2[NPC];
     long long eoff[NPC];
@@ -147,18 +131,17 @@ void rowgemm_kernel(RgArgs g) {
         float* cur = smem + (sl & 1) * SBUF;
         float* nxt = smem + ((sl & 1) ^ 1) * SBUF;
         RG_STORE(nxt);
-        if (DN_RG2_EARLY_EPI(MODE)) epi_fetch();   // (the slice loads have all been consumed: nothing younger is waited on before the epilogue)
+        epi_fetch();   // (the slice loads have all been consumed: nothing younger is waited on before the epilogue)
         RG_COMPUTE(cur);
         __syncthreads();
         ++sl;
     } else {
-        if (DN_RG2_EARLY_EPI(MODE)) epi_fetch();
+        epi_fetch();
     }
     {
         float* cur = smem + (sl & 1) * SBUF;
         RG_COMPUTE(cur);
     }
-    if (!DN_RG2_EARLY_EPI(MODE)) epi_fetch();
 
     // ---------------- epilogue ----------------
     if constexpr (NP == 2) {   // split-fp16: exact power-of-two rescale of the products
@@ -244,7 +227,7 @@ void rowgemm_kernel(RgArgs g) {
 template <int TN, int WR, int WC, int NOUT, int MODE, bool ALIGNED, bool BCOLK, int NP = 3>
 static int rg_launch(const RgArgs& g, int ntiles, hipStream_t stream) {
     const int ncol = (g.N + TN - 1) / TN;
-    constexpr bool X3 = DN_RG_X3 && ALIGNED && NOUT == 2 && TN == 128 && WR * WC == 8;
+    constexpr bool X3 = ALIGNED && NOUT == 2 && TN == 128 && WR * WC == 8;
     const size_t smem = X3 ? (size_t)2 * (DN_TM * 64 * 3 + NOUT * 128 * 64 * 3)
                            : (size_t)2 * (DN_TM * DN_KB + NOUT * DN_KB * TN) * sizeof(float);
 #ifndef DN_EMULATE

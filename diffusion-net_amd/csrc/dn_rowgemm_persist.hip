@@ -4,10 +4,6 @@
 // priorities, phase traces) were measured and rejected one by one; their source lives in tools/experiments/rowgemm_ws_knobs/.
 #include "dn_gemm_tiles.h"
 
-#ifndef DN_RG_X3
-#define DN_RG_X3 1   // keep in step with dn_rowgemm.hip (two-output split-bf16 path)
-#endif
-
 
 // =======================================================================================
 // persistent single-output rowgemm (the heavy N >= 128 products)
@@ -19,9 +15,7 @@
 // the following tile run.  Only the very first prologue and the very last flush of a workgroup are exposed.
 // LDS: 2 x 32 KiB slice buffers + 64 KiB staging = 128 KiB.
 // =======================================================================================
-#ifndef DN_PT_MAX_SLICES
-#define DN_PT_MAX_SLICES 32  // up to K = 1024 (the 3C -> C MLP layer: 12 slices at C = 128, 24 at C = 256; the lock-step exact-f32 fallback took 829 us per launch at C = 256: cfg4 18.9 -> 20.3 M vertices/s)
-#endif
+constexpr int DN_PT_MAX_SLICES = 32;  // up to K = 1024 (the 3C -> C MLP layer: 12 slices at C = 128, 24 at C = 256; the lock-step exact-f32 fallback took 829 us per launch at C = 256: cfg4 18.9 -> 20.3 M vertices/s)
 // Work-unit geometry: 128-row units, 8 waves, one workgroup per CU, split-bf16 planes.  (Measured on MI355X, K = N = 128 product, 158k rows:
 // 68 us; 64-row units with 4 waves and two workgroups per CU: 71-75 us -- twice the B-operand staging per MFMA; non-persistent: 75-80 us.)
 #define DN_PT_ROWS 128

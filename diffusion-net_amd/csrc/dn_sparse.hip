@@ -8,18 +8,13 @@
 // C=128 floats is handled by 32 consecutive lanes, each gathering one float4 per non-zero; column
 // indices / values are wave-broadcast loads.  HBM/L2-bound (about 2 flop per byte).
 #include "dn_common.h"
-#ifndef DN_SP_XCD
-#define DN_SP_XCD 1   // XCD-contiguous row blocks (block b runs on XCD b % 8): 76 vs 81 us on the bench batch (3 rounds)
-#endif
-#ifndef DN_SP_CHUNK
-#ifndef DN_SP_COOP
+constexpr int DN_SP_CHUNK = 8;   // non-zeros gathered per branch-free step (a mesh vertex has ~7 gradient entries)
+// DN_SP_COOP: pattern entries of a row fetched once per row group and shared by shuffles.  Decided by DN_EMULATE alone: the fiber emulator's
+// shuffles are whole-wave barriers and row groups of a wave leave the entry loop at different times, so its build tests the every-lane-loads form.
 #ifdef DN_EMULATE
-#define DN_SP_COOP 0   // (the fiber emulator's shuffles are whole-wave barriers; row groups of a wave leave the entry loop at different times)
+constexpr bool DN_SP_COOP = false;
 #else
-#define DN_SP_COOP 1   // pattern entries of a row fetched once per row group and shared by shuffles (0: every lane loads them)
-#endif
-#endif
-#define DN_SP_CHUNK 8   // non-zeros gathered per branch-free step (a mesh vertex has ~7 gradient entries)
+constexpr bool DN_SP_COOP = true;
 #endif
 
 // MODE is a compile-time copy of s.mode: with the mode tested at run time every unrolled gather step carried its own scalar branches
@@ -35,13 +30,11 @@ __global__ __launch_bounds__(256) void spmm_kernel(SpArgs s, int tpr) {
     const int tid = threadIdx.x;
     const int rl = tid / tpr, cg = tid % tpr;
     const int rows_per_block = 256 / tpr;
-#if DN_SP_XCD   // every XCD walks a contiguous range of row blocks: the ~7 neighbour rows a row gathers mostly live in its L2
+    // every XCD walks a contiguous range of row blocks (block b runs on XCD b % 8): the ~7 neighbour rows a row gathers mostly live in its L2
+    // (76 vs 81 us on the bench batch against block-order rows; the launcher rounds the grid up to a multiple of 8)
     const int per_xcd = (gridDim.x + 7) >> 3;
     const int rb = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     const int row = rb * rows_per_block + rl;
-#else
-    const int row = blockIdx.x * rows_per_block + rl;
-#endif
     // cooperative index loads need every lane of the row's group alive in one wave (the row test below is uniform per group)
     // (and every lane of the group must run every column pass: C a multiple of the group's span)
     const bool coop = DN_SP_COOP && tpr >= DN_SP_CHUNK && tpr <= 64 && s.C % (tpr * VEC) == 0;
@@ -159,7 +152,7 @@ int dn_launch_spmm(const SpArgs& s, hipStream_t stream) {
     int tpr = pow2_at_least(vec ? (s.C + 3) / 4 : s.C);
     if (tpr > 256) tpr = 256;
     const int rpb = 256 / tpr;
-    dim3 grid(DN_SP_XCD ? (((s.nrows + rpb - 1) / rpb) + 7) / 8 * 8 : (s.nrows + rpb - 1) / rpb, 1, 1);
+    dim3 grid((((s.nrows + rpb - 1) / rpb) + 7) / 8 * 8, 1, 1);
     dn_prof_begin(DN_K_SPMM, stream);
     const bool amax = s.o_amax && !(s.op_norm && s.in_amax);
 #define DN_SP_GO(V, M) do { if (amax) DN_LAUNCH((spmm_kernel<V, M, true>), grid, dim3(256, 1, 1), 0, stream, s, tpr); \

@@ -318,9 +318,7 @@ __device__ __forceinline__ void tn_x3_body(const TnArgs& g, const int bx, const 
     }
 }
 
-#ifndef DN_TN_XCD
-#define DN_TN_XCD 1   // products with several output tiles per chunk block (K or C > 128): the tiles of a chunk block run on ONE XCD, back to back (0: the
-#endif                // three-dimensional grid, chunk-major: a chunk's tiles a whole sweep apart; A/B)
+// Products with several output tiles per chunk block (K or C > 128): the tiles of a chunk block run on ONE XCD, back to back (g.lin_ny > 0)
 template <int FLAVOR, int NP>
 __global__ __launch_bounds__(DN_TX_THREADS, 4) void tngemm_x3_kernel(TnArgs g) {
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
@@ -371,10 +369,6 @@ static int tx_launch(const TnArgs& g, dim3 grid, hipStream_t stream) {
     return g.f16 ? tx_launch_np<FLAVOR, 2>(g, grid, stream) : tx_launch_np<FLAVOR, 3>(g, grid, stream);
 }
 
-#ifndef DN_TN_X3
-#define DN_TN_X3 1   // -DDN_TN_X3=0: exact-f32 MFMA in the split-V kernels
-#endif
-
 
 // returns the number of partials written (= gridDim.x) through *npartial
 int dn_launch_tngemm(const TnArgs& g_in, int nchunks, hipStream_t stream) {
@@ -393,9 +387,9 @@ int dn_launch_tngemm(const TnArgs& g_in, int nchunks, hipStream_t stream) {
     const double rows = g.acct_rows;
     dn_prof_begin(DN_K_TNGEMM, stream);
     int err;
-    if (g.aligned && DN_TN_X3) {
+    if (g.aligned) {      // split-bf16 / split-fp16 MFMA; the unaligned products stay on the exact-f32 kernels
         g.lin_nb = g.lin_ny = g.lin_nz = 0;
-        if (DN_TN_XCD && grid.y * grid.z > 1) {
+        if (grid.y * grid.z > 1) {
             g.lin_nb = nblk; g.lin_ny = (int)grid.y; g.lin_nz = (int)grid.z;
             grid = dim3(nblk * grid.y * grid.z, 1, 1);
         }
@@ -404,13 +398,6 @@ int dn_launch_tngemm(const TnArgs& g_in, int nchunks, hipStream_t stream) {
             case DN_TN_COLSUM: err = tx_launch<DN_TN_COLSUM>(g, grid, stream); break;
             case DN_TN_ROWSCALE: err = tx_launch<DN_TN_ROWSCALE>(g, grid, stream); break;
             default: err = tx_launch<DN_TN_PLAIN>(g, grid, stream); break;
-        }
-    } else if (g.aligned) {
-        switch (flavor) {
-            case DN_TN_QA: err = tn_launch<true, DN_TN_QA>(g, grid, stream); break;
-            case DN_TN_COLSUM: err = tn_launch<true, DN_TN_COLSUM>(g, grid, stream); break;
-            case DN_TN_ROWSCALE: err = tn_launch<true, DN_TN_ROWSCALE>(g, grid, stream); break;
-            default: err = tn_launch<true, DN_TN_PLAIN>(g, grid, stream); break;
         }
     } else {
         switch (flavor) {
@@ -428,7 +415,7 @@ int dn_launch_tngemm(const TnArgs& g_in, int nchunks, hipStream_t stream) {
 // Up to DN_TN_MULTI aligned, bias-column-sum ("COLSUM") split-bf16 products in one launch; anything else falls back to separate launches.
 int dn_launch_tngemm_multi(const TnArgs* gs, const int* nchunks, int count, hipStream_t stream) {
     if (count <= 0) return 0;
-    bool ok = count <= DN_TN_MULTI && DN_TN_X3 != 0;
+    bool ok = count <= DN_TN_MULTI;
     for (int i = 0; i < count && ok; ++i) {
         const TnArgs& g = gs[i];
         bool has_qa = false;

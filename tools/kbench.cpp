@@ -320,15 +320,6 @@ int main(int argc, char** argv) {
             report(err, ref);
         }
         endl_();
-        if (trace) {   // libraries built with -DDN_RD_TRACE=<block>: s_memtime stamps of that workgroup's eight waves
-            auto rd = (int (*)(unsigned long long*, int))dlsym(L.h, "dn_debug_rd_trace_read");
-            if (rd) {
-                DC(f(&mb, spec, C, 0, o0, st)); HC(hipStreamSynchronize(st));
-                std::vector<unsigned long long> tb(8 * 64); rd(tb.data(), 8 * 64);
-                unsigned long long t0 = ~0ull; for (int w = 0; w < 8; ++w) t0 = std::min(t0, tb[w * 64]);
-                for (int w = 0; w < 8; ++w) { printf("  wave %d:", w); for (int i = 0; i < 40 && (i == 0 || tb[w * 64 + i] >= tb[w * 64 + i - 1]) ; ++i) printf(" %llu", tb[w * 64 + i] - t0); printf("\n"); }
-            }
-        }
     }
     if (want("diffusion")) {
         auto f = L.sym<int (*)(const dn_mesh_batch_t*, const float*, const float*, int, float*, float*, void*, size_t, void*)>("dn_diffusion_fwd_f32");
@@ -461,30 +452,6 @@ int main(int argc, char** argv) {
             printf("  mean|d_x| %.9e  d_x[V/2] %.7e  mean|dW0| %.9e  max|d_x| %.4e at row %zu  non-finite %zu", ma / got.size(), got[(size_t)(V / 2) * C + 5], mw / gw.size(), mx, imx / C, nbad);
         }
         endl_();
-    }
-    if (trace) {   // libraries built with EXTRA=-DDN_WS_TRACE=<block>: stamps of the wave-specialised row GEMM (MFMA wave 0: 3 per slice, loader wave 4: 5)
-        auto rd = (int (*)(unsigned long long*, int))dlsym(L.h, "dn_debug_rd_trace_read");
-        if (rd) {
-            for (const char* which : {"linear", "from_basis"}) {
-                if (std::string(which) == "linear") DC(lin(&mb, x, C, W, b, C, 1, nullptr, o0, st));
-                else DC((L.sym<int (*)(const dn_mesh_batch_t*, const float*, int, int, float*, void*)>("dn_from_basis_f32"))(&mb, spec, C, 0, o0, st));
-                HC(hipStreamSynchronize(st));
-                std::vector<unsigned long long> tb(12 * 256); rd(tb.data(), 12 * 256);
-                printf("== trace %s\n", which);
-                auto dump = [&](int w, int per, const char* names) {
-                    printf(" wave %d (%s), deltas per iteration:\n", w, names);
-                    const unsigned long long* t = &tb[(size_t)w * 256];
-                    for (int it = 0; it < 20 && (it + 1) * per < 256; ++it) {
-                        printf("  it %2d:", it);
-                        for (int k = 0; k < per; ++k) printf(" %6llu", t[it * per + k + 1] - t[it * per + k]);
-                        printf("   | iter %6llu\n", t[(it + 1) * per] - t[it * per]);
-                    }
-                };
-                dump(0, 3, "MFMA: reads+mma issue | park | barrier");
-                const int per = getenv("WS_TR_PER") ? atoi(getenv("WS_TR_PER")) : 6;   // 6: DN_WS_EARLY=1 (wait|split|request|LDS put|pieces|barrier); 5: =0 (wait|stage|pieces|request|barrier)
-                dump(4, per, per == 6 ? "loader: vm wait | split | advance+request | LDS writes | pieces | barrier" : "loader: vm wait | split+LDS writes | pieces | advance+request | barrier");
-            }
-        }
     }
     if (getenv("KB_CLK")) {   // libraries built with EXTRA=-DDN_CLK_TRACE: shader clock each kernel ran at = d(s_memtime) / d(s_memrealtime at 100 MHz), last launch
         for (const char* nm : {"chain_fwd", "chain_bwd", "tn_multi", "tn_da"}) {
