@@ -114,6 +114,7 @@ _SIGNATURES = {
     "dn_knn_max_k": (C.c_int, []),
     "dn_knn_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "dn_knn_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "dn_cloud_operators_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [_vp] * 9),
     "dn_coo_to_csr_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "dn_coo_to_csr_i64": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int] + [_vp] * 7 + [_vp, C.c_size_t, _vp]),
     "dn_checksum128": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp, _vp]),

@@ -256,6 +256,62 @@ def knn(src, tgt, k, largest=False, omit_diagonal=False, n_split=0):
     return _knn_launch(src, tgt, k, bool(largest), bool(omit_diagonal), n_split)
 
 
+@_on_device
+def _cloud_launch(points, nbr, normals_in):
+    n, k = nbr.shape
+    dev = points.device
+    normals = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    frames = torch.empty(n, 3, 3, dtype=torch.float32, device=dev)
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(n * (k + 1), dtype=torch.int32, device=dev)
+    vx = torch.empty(n * (k + 1), dtype=torch.float32, device=dev)
+    vy = torch.empty(n * (k + 1), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        rowptr.zero_()
+    _hip.check(_hip.lib().dn_cloud_operators_f32(points.data_ptr(), n, nbr.data_ptr(), k, _hip.ptr(normals_in), normals.data_ptr(),
+                                                 frames.data_ptr(), rowptr.data_ptr(), col.data_ptr(), vx.data_ptr(), vy.data_ptr(),
+                                                 status.data_ptr(), _hip.stream_of(points)), "dn_cloud_operators_f32")
+    return normals, frames, rowptr, col, vx, vy, status
+
+
+def cloud_operators(points, nbr, normals=None):
+    """Normal, tangent frame and gradient stencil of every point of a cloud from the indices of its neighbours (geometry.py:92-99, 114-123,
+    151-273 for a cloud; include/diffnet_hip.h: dn_cloud_operators_f32), forward only.  ``points`` [N, 3] fp32, ``nbr`` [N, k] int64 as
+    ``ops.knn(points, points, k, omit_diagonal=True)`` returns them, ``normals`` [N, 3] fp32 or None (estimated).
+    -> (normals [N, 3], frames [N, 3, 3], rowptr [N + 1] int32, col [N (k + 1)] int32, vx, vy [N (k + 1)] fp32): row i of the gradient
+    operator has k + 1 entries, column i first, then the neighbours in ``nbr`` order.  Raises ``IndexError`` if a row of ``nbr`` holds an
+    index outside [0, N) (reading the status word waits for the kernel)."""
+    _hip.require_device(points)
+    _hip.require_device(nbr)
+    points = _f32c(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("cloud_operators takes [N, 3] points (got %s)" % (tuple(points.shape),))
+    if nbr.dim() != 2 or nbr.shape[0] != points.shape[0]:
+        raise ValueError("cloud_operators takes [N, k] neighbour indices for [N, 3] points (got %s for %s)" % (tuple(nbr.shape), tuple(points.shape)))
+    if nbr.dtype != torch.int64:
+        raise TypeError("cloud_operators takes int64 neighbour indices (got %s)" % nbr.dtype)
+    if nbr.device != points.device:
+        raise RuntimeError("cloud_operators: points on %s, neighbour indices on %s" % (points.device, nbr.device))
+    n, k = nbr.shape
+    if not 1 <= k <= _hip.KNN_MAX_K:
+        raise ValueError("cloud_operators kernel takes 1 <= k <= %d neighbours (got %d)" % (_hip.KNN_MAX_K, k))
+    if n * (k + 1) > 2 ** 31 - 1:
+        raise ValueError("cloud_operators: %d x %d row entries do not fit a 32-bit row pointer" % (n, k + 1))
+    if normals is not None:
+        _hip.require_device(normals)
+        normals = _f32c(normals)
+        if tuple(normals.shape) != (n, 3):
+            raise ValueError("cloud_operators takes [N, 3] normals (got %s)" % (tuple(normals.shape),))
+        if normals.device != points.device:
+            raise RuntimeError("cloud_operators: points on %s, normals on %s" % (points.device, normals.device))
+    *out, status = _cloud_launch(points, nbr.contiguous(), normals)
+    bad = int(status.item())
+    if bad:
+        raise IndexError("cloud_operators: %d row(s) of the neighbour table hold an index outside [0, %d)" % (bad, n))
+    return tuple(out)
+
+
 # ----------------------------------------------------------------------------------------------
 # gradient sinks: a parameter may carry ``_dn_grad_sink`` (set by dist.FlatParams: its slice of the flat
 # gradient bucket).  Backward then ACCUMULATES the parameter gradients of a whole op into their sinks with

@@ -10,7 +10,9 @@ numpy/scipy only, fully vectorised:
 
 and the npz operator cache of ``get_operators`` (geometry.py:426-570) with the same file naming
 (sha1(verts,faces)_<bucket>.npz) and the same keys, so caches written by either implementation are interchangeable.
-Triangle meshes only: the point-cloud branch needs robust_laplacian's point-cloud Laplacian and is not restated.
+Point clouds (empty ``faces``): normals, frames and gradients come from ``geometry.cloud_operators`` (HIP kernel on a ROCm device,
+vectorised numpy otherwise); only the point-cloud LAPLACIAN of robust_laplacian is not restated -- ``compute_operators`` takes it from
+its ``laplacian=`` argument or from that package if it is installed.
 """
 from __future__ import annotations
 
@@ -81,6 +83,15 @@ def vertex_normals(verts: np.ndarray, faces: np.ndarray) -> np.ndarray:
     return normals
 
 
+def neighborhood_normal(points: np.ndarray) -> np.ndarray:
+    """(N,K,3) neighbourhoods centred on their point -> (N,3) unit normals: the right singular vector of the smallest singular value of
+    every K x 3 block, in the dtype of ``points`` and with the sign LAPACK returns (geometry.py:92-99).  numpy in, numpy out.
+    (K < 3, where the reference's reduced SVD has no third vector and raises: the full one, whose last vector spans the null space.)"""
+    vh = np.linalg.svd(points, full_matrices=points.shape[1] < 3)[2]
+    normal = vh[:, 2, :]
+    return normal / np.linalg.norm(normal, axis=-1, keepdims=True)
+
+
 def tangent_frames(normals: np.ndarray) -> np.ndarray:
     """(V,3,3) rows = (basisX, basisY, normal): basisX is e_x (or e_y where the normal is within ~26 degrees of e_x)
     projected onto the tangent plane, basisY = n x basisX (geometry.py:151-177)."""
@@ -103,13 +114,18 @@ def gradient_operator(verts: np.ndarray, frames: np.ndarray, edges: np.ndarray) 
     Per vertex, with t_e the 2-D tangent coordinates of edge e:  G = sum_e t_e t_e^T + 1e-5 I,
     coefficient of neighbour j_e = G^-1 t_e, coefficient of v itself = -sum_e G^-1 t_e.
     (Vectorised restatement of the per-vertex solve of geometry.py:222-263.)"""
-    V = verts.shape[0]
     tail, tip = edges[0], edges[1]
     keep = tail != tip
     tail, tip = tail[keep], tip[keep]
     d = verts[tip] - verts[tail]
     tx = np.einsum("ij,ij->i", d, frames[tail, 0])
     ty = np.einsum("ij,ij->i", d, frames[tail, 1])
+    return gradient_from_tangents(verts.shape[0], tail, tip, tx, ty)
+
+
+def gradient_from_tangents(V: int, tail: np.ndarray, tip: np.ndarray, tx: np.ndarray, ty: np.ndarray) -> sp.csc_matrix:
+    """The per-vertex 2 x 2 solves of ``gradient_operator`` on edges (tail -> tip, none with tail == tip) whose tangent coordinates
+    (tx, ty) in the tail's frame are given."""
     gxx = np.bincount(tail, weights=tx * tx, minlength=V) + GRAD_REG
     gxy = np.bincount(tail, weights=tx * ty, minlength=V)
     gyy = np.bincount(tail, weights=ty * ty, minlength=V) + GRAD_REG
@@ -152,12 +168,57 @@ def _to_torch_sparse(mat, device, dtype):
     return torch.sparse_coo_tensor(idx, torch.from_numpy(coo.data.astype(np.float64)), coo.shape).coalesce().to(device=device, dtype=dtype)
 
 
-def compute_operators(verts, faces, k_eig, normals=None):
+def _cloud_laplacian(v64, laplacian):
+    """(L, massvec) of a point cloud: the caller's pair, the caller's function of the fp64 positions, or robust_laplacian's."""
+    if laplacian is None:
+        try:
+            import robust_laplacian
+        except ImportError as err:
+            raise ImportError(
+                "compute_operators on a point cloud (empty faces) needs a point-cloud Laplacian, which this package does not restate: "
+                "either pass laplacian=(L, massvec) or laplacian=<callable: fp64 positions [V,3] -> (L, M)>, "
+                "or install the robust_laplacian package (its point_cloud_laplacian is then used, as in the reference)") from err
+        laplacian = robust_laplacian.point_cloud_laplacian
+    L, M = laplacian(v64) if callable(laplacian) else laplacian
+    if isinstance(M, torch.Tensor):
+        M = M.detach().cpu().numpy()
+    mass = M.diagonal() if sp.issparse(M) or np.ndim(M) == 2 else np.asarray(M)
+    mass = np.asarray(mass, dtype=np.float64).reshape(-1)
+    L = sp.csr_matrix(L).astype(np.float64)
+    if L.shape != (v64.shape[0], v64.shape[0]) or mass.shape != (v64.shape[0],):
+        raise ValueError("laplacian: L %s and mass %s do not fit %d points" % (L.shape, mass.shape, v64.shape[0]))
+    return L, mass
+
+
+def _compute_cloud_operators(verts, k_eig, normals, laplacian, n_neighbors_cloud=30):
+    """The point-cloud branch of ``compute_operators`` (geometry.py:306-392 with is_cloud)."""
+    from .geometry import cloud_operators          # (geometry imports this module)
+    device, dtype = verts.device, verts.dtype
+    frames, gradX, gradY = cloud_operators(verts, n_neighbors_cloud, normals=normals)
+    v64 = verts.detach().cpu().numpy().astype(np.float64)
+    L, mass = _cloud_laplacian(v64, laplacian)
+    if np.isnan(L.data).any():
+        raise RuntimeError("NaN Laplace matrix")
+    if np.isnan(mass).any():
+        raise RuntimeError("NaN mass matrix")
+    evals, evecs = laplacian_eigenbasis(L, mass, k_eig)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)
+    return frames, t(mass), _to_torch_sparse(L, device, dtype), t(evals), t(evecs), gradX, gradY
+
+
+def compute_operators(verts, faces, k_eig, normals=None, *, laplacian=None):
     """Same contract as the reference's ``compute_operators`` (geometry.py:276-392), torch in / torch out:
-    returns (frames [V,3,3], massvec [V], L sparse, evals [k], evecs [V,k], gradX sparse, gradY sparse)."""
+    returns (frames [V,3,3], massvec [V], L sparse, evals [k], evecs [V,k], gradX sparse, gradY sparse).
+
+    Empty ``faces``: a point cloud.  Frames and gradients are those of ``geometry.cloud_operators`` (30 neighbours, as the reference);
+    the Laplacian and the mass come from ``laplacian`` -- ``(L scipy sparse, massvec)`` or a callable taking the fp64 positions [V,3] and
+    returning ``(L, M)`` (M a diagonal sparse matrix or a vector) -- or, without it, from ``robust_laplacian.point_cloud_laplacian`` if
+    that package is installed (ImportError otherwise)."""
     device, dtype = verts.device, verts.dtype
     if faces.numel() == 0:
-        raise NotImplementedError("point clouds need robust_laplacian's point-cloud Laplacian (not restated); triangle meshes only")
+        return _compute_cloud_operators(verts, k_eig, normals, laplacian)
+    if laplacian is not None:
+        raise ValueError("laplacian= is for point clouds (empty faces); a triangle mesh gets its cotan Laplacian")
     v = verts.detach().cpu().numpy().astype(np.float64)
     f = faces.detach().cpu().numpy().astype(np.int64)
     n = vertex_normals(v, f) if normals is None else normals.detach().cpu().numpy().astype(np.float64)
@@ -182,11 +243,11 @@ def _sparse_to_csc(t):
     return sp.coo_matrix((val, (idx[0], idx[1])), shape=tuple(t.shape)).tocsc()
 
 
-def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, overwrite_cache=False):
+def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, overwrite_cache=False, *, laplacian=None):
     """``compute_operators`` behind the reference's on-disk npz cache (geometry.py:426-570): same key derivation, same
     file names, same array names (float32 payload, CSC triplets for L / gradX / gradY), so either implementation can
     read the other's cache.  A hit is verified against the stored verts/faces; an entry with too few eigenpairs is
-    rebuilt."""
+    rebuilt.  ``laplacian``: passed on to ``compute_operators`` (point clouds)."""
     device, dtype = verts.device, verts.dtype
     v_np, f_np = verts.detach().cpu().numpy(), faces.detach().cpu().numpy()
     if np.isnan(v_np).any():
@@ -215,7 +276,7 @@ def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, over
                         _to_torch_sparse(rd("gradY"), device, dtype))
             except Exception:              # unreadable entry: rebuild in place  # noqa: BLE001
                 break
-    out = compute_operators(verts, faces, k_eig, normals=normals)
+    out = compute_operators(verts, faces, k_eig, normals=normals, laplacian=laplacian)
     if path is not None:
         frames, mass, L, evals, evecs, gX, gY = out
         f32 = lambda a: a.detach().cpu().numpy().astype(np.float32)
@@ -228,11 +289,12 @@ def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, over
     return out
 
 
-def get_all_operators(verts_list, faces_list, k_eig, op_cache_dir=None, normals=None):
-    """Lists in, seven lists out (geometry.py:395-424)."""
+def get_all_operators(verts_list, faces_list, k_eig, op_cache_dir=None, normals=None, *, laplacian=None):
+    """Lists in, seven lists out (geometry.py:395-424).  ``laplacian``: None, one value for every entry, or a list with one per entry."""
     cols = [[] for _ in range(7)]
     for i, (v, f) in enumerate(zip(verts_list, faces_list)):
-        res = get_operators(v, f, k_eig, op_cache_dir, normals=None if normals is None else normals[i])
+        lap = laplacian[i] if isinstance(laplacian, list) else laplacian
+        res = get_operators(v, f, k_eig, op_cache_dir, normals=None if normals is None else normals[i], laplacian=lap)
         for c, r in zip(cols, res):
             c.append(r)
     return tuple(cols)

@@ -339,6 +339,29 @@ size_t dn_knn_workspace_bytes(int n_src, int n_tgt, int dim, int k, int n_split)
 int dn_knn_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int largest, int omit_diagonal, int n_split,
                float* dist, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- point-cloud frames and gradient stencils (geometry.py:92-99, 114-123, 151-206, 209-273 for a cloud): what the reference computes
+ *      per point from the indices of its k nearest neighbours, in one pass (dn_cloud.hip).  pts [n,3] fp32; nbr [n,k] int64 as dn_knn_f32
+ *      writes them (omit_diagonal).  With e_j = pts[nbr[i,j]] - pts[i] (centred on the point, not on the neighbourhood mean):
+ *        normal  the unit eigenvector of sum_j e_j e_j^T for its smallest eigenvalue (= the last right singular vector of the k x 3 matrix
+ *                of the e_j).  The reference's sign is whatever LAPACK returns; here the component of largest magnitude is positive, equal
+ *                magnitudes going to the lower axis.  Rank-deficient neighbourhoods (collinear, coincident) give a finite unit vector.
+ *                normals_in != NULL: those [n,3] normals are used as they are, the estimate is skipped and `normals` is a copy.
+ *        frame   rows basisX, basisY, normal: basisX = c - n (n.c) with c = e_x where |n_x| < 0.9, else e_y, divided by (|basisX| + 1e-6)
+ *                (the reference's normalize(): deliberately not quite unit); basisY = n x basisX.
+ *        row i   of the complex gradient operator, real part in g_vx, imaginary part in g_vy: with t_j = (e_j.basisX, e_j.basisY) and
+ *                G = sum_j t_j t_j^T + 1e-5 I the coefficient of neighbour j is G^-1 t_j and that of i itself -sum_j G^-1 t_j.  Every row
+ *                has k + 1 entries, g_rowptr[i] = i (k + 1): entry 0 is column i, entries 1..k the neighbours in nbr order.  A neighbour
+ *                equal to i (the reference drops tail == tip edges) contributes nothing: its slot carries column i and the value 0, so
+ *                summing equal columns of a row reproduces the reference.
+ *      Inputs and outputs are fp32; everything from the coordinate differences on is fp64, rounded once at the store; the result is
+ *      bit-identical from run to run.  status: one device int32, set to the number of rows that held an index outside [0,n); such a row
+ *      reads nothing through it and writes zeros (normal, frame, columns, values; its g_rowptr entry stays i (k + 1)).  The caller reads the
+ *      word at its next synchronisation point.
+ *      Returns 0 on success (n == 0: nothing is launched) and non-zero WITHOUT launching for k < 1, k > DN_KNN_MAX_K, n < 0,
+ *      n (k + 1) > INT32_MAX, or a NULL pointer other than normals_in while n > 0. */
+int dn_cloud_operators_f32(const float* pts, int n, const int64_t* nbr, int k, const float* normals_in, float* normals, float* frames,
+                           int32_t* g_rowptr, int32_t* g_col, float* g_vx, float* g_vy, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
