@@ -16,6 +16,7 @@ MAX_MLP = 8
 BLOCK_AMAX_WORDS = 16       # include/diffnet_hip.h: DN_BLOCK_AMAX_WORDS
 HEAD_MAX_CLASSES = 2048   # dn_head.hip: 64 lanes x DN_HEAD_CPL classes per row
 KNN_MAX_K = 32            # include/diffnet_hip.h: DN_KNN_MAX_K
+FMAP_MAX_K = 64           # include/diffnet_hip.h: DN_FMAP_MAX_K
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # DN_LIB_VARIANT=<tag> selects libdiffnet_hip_<tag>.so (same sources, other build flags) for A/B experiments
 _VARIANT = os.environ.get("DN_LIB_VARIANT", "")
@@ -115,6 +116,10 @@ _SIGNATURES = {
     "dn_knn_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "dn_knn_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
     "dn_cloud_operators_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [_vp] * 9),
+    "dn_fmap_max_k": (C.c_int, []),
+    "dn_fmap_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "dn_fmap_solve_fwd_f32": (C.c_int, [_vp] * 4 + [C.c_int] * 3 + [C.c_float, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "dn_fmap_solve_bwd_f32": (C.c_int, [_vp] * 5 + [C.c_int] * 3 + [C.c_float, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "dn_coo_to_csr_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "dn_coo_to_csr_i64": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int] + [_vp] * 7 + [_vp, C.c_size_t, _vp]),
     "dn_checksum128": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp, _vp]),

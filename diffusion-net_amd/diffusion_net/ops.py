@@ -313,6 +313,91 @@ def cloud_operators(points, nbr, normals=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# functional maps: the regularised spectral solve (include/diffnet_hip.h: dn_fmap_solve_*_f32)
+# ----------------------------------------------------------------------------------------------
+def _fmap_ws(A):
+    P, K, F = A.shape
+    return _hip.workspace(A.device, max(int(_hip.lib().dn_fmap_workspace_bytes(P, K, F)), 1024))
+
+
+@_on_device
+def fmap_solve_fwd(A, B, evals_x, evals_y, lam, status=None):
+    """A, B [P, K, F], evals [P, K] (fp32, contiguous) -> C [P, K, K]; ``status``: an int32 word that receives the number of singular rows."""
+    P, K, F = A.shape
+    Cm = torch.empty(P, K, K, dtype=torch.float32, device=A.device)
+    ws = _fmap_ws(A)
+    _hip.check(_hip.lib().dn_fmap_solve_fwd_f32(A.data_ptr(), B.data_ptr(), evals_x.data_ptr(), evals_y.data_ptr(), P, K, F, float(lam),
+                                                Cm.data_ptr(), ws.data_ptr(), ws.numel(), _hip.ptr(status), _hip.stream_of(A)),
+               "dn_fmap_solve_fwd_f32")
+    return Cm
+
+
+@_on_device
+def fmap_solve_bwd(A, B, evals_x, evals_y, lam, d_C):
+    """-> (dA, dB) [P, K, F]; recomputes the factorisations from A, B and the eigenvalues."""
+    P, K, F = A.shape
+    dA, dB = torch.empty_like(A), torch.empty_like(B)
+    ws = _fmap_ws(A)
+    _hip.check(_hip.lib().dn_fmap_solve_bwd_f32(A.data_ptr(), B.data_ptr(), evals_x.data_ptr(), evals_y.data_ptr(), d_C.data_ptr(), P, K, F,
+                                                float(lam), dA.data_ptr(), dB.data_ptr(), ws.data_ptr(), ws.numel(), None, _hip.stream_of(A)),
+               "dn_fmap_solve_bwd_f32")
+    return dA, dB
+
+
+class FmapSolveFn(torch.autograd.Function):
+    """C[p, i, :] = (A_p A_p^T + lam diag_j (evals_x[p, j] - evals_y[p, i])^2)^-1 (B_p A_p^T)[i, :]; gradients for A and B only."""
+
+    @staticmethod
+    def forward(ctx, A, B, evals_x, evals_y, lam, status):
+        ctx.lam = lam
+        ctx.save_for_backward(A, B, evals_x, evals_y)
+        return fmap_solve_fwd(A, B, evals_x, evals_y, lam, status)
+
+    @staticmethod
+    def backward(ctx, d_C):
+        A, B, evals_x, evals_y = ctx.saved_tensors
+        dA, dB = fmap_solve_bwd(A, B, evals_x, evals_y, ctx.lam, _f32c(d_C))
+        return dA, dB, None, None, None, None
+
+
+def _fmap_operands(A, B, evals_x, evals_y, lam):
+    """The checks of ``fmap_solve``: -> contiguous fp32 [P, K, F], [P, K] operands, the host float of lam and whether the call was unbatched."""
+    for t in (A, B, evals_x, evals_y):
+        _hip.require_device(t)
+    A, B, evals_x, evals_y = _f32c(A), _f32c(B), _f32c(evals_x), _f32c(evals_y)
+    if A.dim() not in (2, 3) or A.shape != B.shape or A.shape[-1] < 1:
+        raise ValueError("fmap_solve takes two [K, F] or [P, K, F] coefficient tensors of one shape (got %s and %s)" % (tuple(A.shape), tuple(B.shape)))
+    if tuple(evals_x.shape) != tuple(A.shape[:-1]) or tuple(evals_y.shape) != tuple(A.shape[:-1]):
+        raise ValueError("fmap_solve takes square maps: %s eigenvalues for both shapes (got %s and %s)" % (
+            tuple(A.shape[:-1]), tuple(evals_x.shape), tuple(evals_y.shape)))
+    if len({t.device for t in (A, B, evals_x, evals_y)}) != 1:
+        raise RuntimeError("fmap_solve: operands on %s" % ", ".join(str(t.device) for t in (A, B, evals_x, evals_y)))
+    if not 1 <= A.shape[-2] <= _hip.FMAP_MAX_K:
+        raise ValueError("fmap_solve kernel takes 1 <= K <= %d (got %d)" % (_hip.FMAP_MAX_K, A.shape[-2]))
+    if evals_x.requires_grad or evals_y.requires_grad or (isinstance(lam, torch.Tensor) and lam.requires_grad):
+        raise ValueError("fmap_solve has gradients for the coefficients only, not for the eigenvalues or lam")
+    squeeze = A.dim() == 2
+    if squeeze:
+        A, B, evals_x, evals_y = A[None], B[None], evals_x[None], evals_y[None]
+    return A, B, evals_x, evals_y, float(lam), squeeze
+
+
+def fmap_solve(A, B, evals_x, evals_y, lam, check=False):
+    """Functional map of spectral coefficients ``A``, ``B`` [K, F] or [P, K, F] and eigenvalues [K] or [P, K] (fp32) -> C [K, K] or
+    [P, K, K]: row i is (A A^T + lam diag_j (evals_x[j] - evals_y[i])^2)^-1 (B A^T)[i, :] (include/diffnet_hip.h: dn_fmap_solve_fwd_f32),
+    differentiable in A and B.  A singular row comes back as NaN; ``check=True`` reads the device's count of them -- which waits for the
+    kernels -- and raises ``RuntimeError`` instead.  The default reads nothing back."""
+    A, B, evals_x, evals_y, lam, squeeze = _fmap_operands(A, B, evals_x, evals_y, lam)
+    status = torch.empty(1, dtype=torch.int32, device=A.device) if check else None
+    Cm = FmapSolveFn.apply(A, B, evals_x, evals_y, lam, status)
+    if check:
+        bad = int(status.item()) if A.shape[0] else 0
+        if bad:
+            raise RuntimeError("fmap_solve: %d row(s) of the map have a singular system" % bad)
+    return Cm[0] if squeeze else Cm
+
+
+# ----------------------------------------------------------------------------------------------
 # gradient sinks: a parameter may carry ``_dn_grad_sink`` (set by dist.FlatParams: its slice of the flat
 # gradient bucket).  Backward then ACCUMULATES the parameter gradients of a whole op into their sinks with
 # one multi-tensor add and returns None for them, instead of handing ~10 small tensors per block to

@@ -297,3 +297,37 @@ def knn(src: Tensor, tgt: Tensor, k: int, largest: bool, omit_diagonal: bool) ->
 @knn.register_fake
 def _(src, tgt, k, largest, omit_diagonal):
     return src.new_empty(src.shape[0], k, dtype=torch.float32), src.new_empty(src.shape[0], k, dtype=torch.int64)   # ops.knn is fp32
+
+
+# ------------------------------------------------------------------------------------------------ functional maps (regularised spectral solve)
+@_op("diffusion_net::fmap_solve")
+def fmap_solve(A: Tensor, B: Tensor, evals_x: Tensor, evals_y: Tensor, lam: float) -> Tensor:
+    A, B, evals_x, evals_y, lam, squeeze = ops._fmap_operands(A, B, evals_x, evals_y, lam)
+    Cm = ops.fmap_solve_fwd(A, B, evals_x, evals_y, lam, None)
+    return Cm[0] if squeeze else Cm
+
+
+@fmap_solve.register_fake
+def _(A, B, evals_x, evals_y, lam):
+    return A.new_empty(*A.shape[:-1], A.shape[-2], dtype=torch.float32)   # ops.fmap_solve is fp32
+
+
+@_op("diffusion_net::fmap_solve_bwd")
+def fmap_solve_bwd(d_C: Tensor, A: Tensor, B: Tensor, evals_x: Tensor, evals_y: Tensor, lam: float) -> Tuple[Tensor, Tensor]:
+    A3, B3, evals_x, evals_y, lam, _ = ops._fmap_operands(A, B, evals_x, evals_y, lam)
+    dA, dB = ops.fmap_solve_bwd(A3, B3, evals_x, evals_y, lam, _c(d_C))
+    return dA.reshape(A.shape), dB.reshape(B.shape)
+
+
+@fmap_solve_bwd.register_fake
+def _(d_C, A, B, evals_x, evals_y, lam):
+    return A.new_empty(A.shape, dtype=torch.float32), B.new_empty(B.shape, dtype=torch.float32)
+
+
+def _fmap_setup(ctx, inputs, output):
+    ctx.lam = inputs[4]
+    ctx.save_for_backward(*inputs[:4])
+
+
+fmap_solve.register_autograd(lambda ctx, grad: (*fmap_solve_bwd(grad.contiguous(), *ctx.saved_tensors, ctx.lam), None, None, None),
+                             setup_context=_fmap_setup)

@@ -362,6 +362,32 @@ int dn_knn_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim
 int dn_cloud_operators_f32(const float* pts, int n, const int64_t* nbr, int k, const float* normals_in, float* normals, float* frames,
                            int32_t* g_rowptr, int32_t* g_col, float* g_vx, float* g_vy, int32_t* status, void* stream);
 
+/* ---- functional maps (experiments/functional_correspondence/fmaps_model.py:11-40): the regularised spectral solve and its backward
+ *      (dn_fmap.hip).  A, B [P, K, F] fp32 row-major: the spectral coefficients of the features of shapes x and y of P pairs;
+ *      evals_x, evals_y [P, K] fp32; lam: the regularisation weight.  With G = A A^T, H = B A^T and
+ *      D_i = diag_j (evals_x[j] - evals_y[i])^2, row i of C [P, K, K] is
+ *          c_i = (G + lam D_i)^-1 H[i, :]^T
+ *      -- K symmetric positive (semi-)definite K x K systems that share G, each factored once by Cholesky without pivoting.
+ *      bwd: with dC [P, K, K] = dL/dC, u_i = (G + lam D_i)^-1 dC[i, :]^T, U the matrix of rows u_i^T and dG = -U^T C:
+ *          dA = (dG + dG^T) A + U^T B,   dB = U A      ([P, K, F] fp32; no gradient for the eigenvalues or lam).
+ *      bwd recomputes G, the factorisations and c_i from A, B and the eigenvalues: it takes no stored C, whose fp32 rounding would
+ *      enter the gradient.
+ *      Operands and results are fp32; everything from the loads on is fp64 (lam is widened as it is), rounded once at the store.  No
+ *      float atomics: the result is bit-identical from run to run.  Two launches forward, three backward, no host synchronisation.
+ *      A pivot that is not a positive finite number (a singular system, a non-finite operand) faults nothing and reads nothing outside the
+ *      matrix: fwd stores that row of C as NaN, bwd stores NaN in all of that pair's dA and dB.  status (may be NULL): one device int32
+ *      that the call first sets to 0 and then raises by one for every such row; the caller reads it at its next synchronisation point.
+ *      Workspace: dn_fmap_workspace_bytes(P, K, F) bytes serve either direction (G, H, and for bwd C and U, in fp64).
+ *      Returns 0 on success (P == 0: nothing is launched) and non-zero WITHOUT launching for K < 1, K > DN_FMAP_MAX_K, F < 1 (or
+ *      F > 65535 * 32), P < 0, a NULL operand, result or workspace while P > 0, or a workspace smaller than the query says. */
+#define DN_FMAP_MAX_K 64
+int dn_fmap_max_k(void);
+size_t dn_fmap_workspace_bytes(int P, int K, int F);
+int dn_fmap_solve_fwd_f32(const float* A, const float* B, const float* evals_x, const float* evals_y, int P, int K, int F, float lam, float* C,
+                          void* ws, size_t ws_bytes, int32_t* status, void* stream);
+int dn_fmap_solve_bwd_f32(const float* A, const float* B, const float* evals_x, const float* evals_y, const float* dC, int P, int K, int F, float lam,
+                          float* dA, float* dB, void* ws, size_t ws_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
