@@ -383,8 +383,12 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
                 // ---- CSR gather of the row: gx = sum_j vx_j xd[col_j], gy likewise (entry order, fmaf: bit for bit spmm_kernel's sums)
                 float gxv[NT][4], gyv[NT][4];
                 [[maybe_unused]] int beg = 0, end = 0, nmax = 0;
+                // a wave runs to its longest row; the steps past a row's own end carry weight 0 and gather THAT row of xd (its own mesh, always
+                // in range): entry 0 of the whole pattern points into mesh 0, and 0 x NaN from there reached every mesh of the batch
+                [[maybe_unused]] int padc = 0;
                 if constexpr (!SG && !PRE) {
                     beg = hh ? begh[HH - 1] : begh[0]; end = hh ? endh[HH - 1] : endh[0];
+                    padc = hh ? rch[HH - 1] : rch[0];
                     nmax = (int)ch_wave_max((float)(end - beg));
                 }
                 if constexpr (PRE) {
@@ -446,13 +450,14 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { gxv[nt][e] = 0.f; gyv[nt][e] = 0.f; }
                     int cj[GCH]; float wx[GCH], wy[GCH];
-                    auto entries = [&](int j0) {      // pattern entries j0 .. j0 + GCH - 1 of the row (past its end: entry 0 with weight 0)
+                    auto entries = [&](int j0) {      // pattern entries j0 .. j0 + GCH - 1 of the row (past its end: the row itself with weight 0)
 #pragma unroll
                         for (int u = 0; u < GCH; ++u) {
                             const int idx = beg + j0 + u;
                             const bool in = idx < end;
                             const int ii = in ? idx : 0;
-                            cj[u] = a.col[ii];
+                            const int cl = a.col[ii];     // (loaded whether or not it is used: a select, not a branch)
+                            cj[u] = in ? cl : padc;
                             wx[u] = in ? a.vx[ii] : 0.f;
                             wy[u] = in ? a.vy[ii] : 0.f;
                         }
@@ -495,13 +500,14 @@ __global__ __launch_bounds__(64 * NW) DN_WAVES_PER_EU(C >= 256 ? 1 : 2) void cha
                         float4 bx[NI], by[NI];            // sums of row RPI * i + rsub of the half, channels 4 cc .. 4 cc + 3
 #pragma unroll
                         for (int i = 0; i < NI; ++i) { bx[i] = make_float4(0.f, 0.f, 0.f, 0.f); by[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
-                        auto entries = [&](int j0, int (&cjv)[GCR], float (&wxv)[GCR], float (&wyv)[GCR]) {   // entries j0 .. j0 + GCR - 1 of this lane's row (past its end: entry 0, weight 0)
+                        auto entries = [&](int j0, int (&cjv)[GCR], float (&wxv)[GCR], float (&wyv)[GCR]) {   // entries j0 .. j0 + GCR - 1 of this lane's row (past its end: the row itself, weight 0)
 #pragma unroll
                             for (int u = 0; u < GCR; ++u) {
                                 const int idx = beg + j0 + u;
                                 const bool in = idx < end;
                                 const int ii = in ? idx : 0;
-                                cjv[u] = a.col[ii];
+                                const int cl = a.col[ii];
+                                cjv[u] = in ? cl : padc;
                                 wxv[u] = in ? a.vx[ii] : 0.f;
                                 wyv[u] = in ? a.vy[ii] : 0.f;
                             }
