@@ -7,6 +7,8 @@ The host-side operator precompute keeps the reference's names here (``compute_op
 (numpy/scipy restatement).  ``find_knn`` is the nearest-neighbour query of the evaluation scripts and of the
 point-cloud operators: ``vertex_normals``, ``build_tangent_frames``, ``build_grad_point_cloud`` (the reference's names) and
 ``cloud_operators`` (normals, frames and gradient stencils of a cloud in one HIP pass over its neighbour table).
+``geodesic_label_errors`` and ``get_all_pairs_geodesic_distance`` are the evaluation metric of the correspondence experiments: all-pairs
+distances on the mesh's Steiner-point graph (``mesh_distance_graph``, ``geodesic_distances``), swept on the device by dn_geodesic.hip.
 """
 from collections import namedtuple
 
@@ -246,3 +248,215 @@ def cloud_operators(verts, n_neighbors_cloud=30, normals=None):
     frames = _frames_of_normals(normals.to(device=verts.device, dtype=verts.dtype))
     grad = build_grad_point_cloud(verts, frames, n_neighbors_cloud)
     return (frames, _pre._to_torch_sparse(grad.real, verts.device, verts.dtype), _pre._to_torch_sparse(grad.imag, verts.device, verts.dtype))
+
+
+# ----------------------------------------------------------------------------------------------
+# geodesic evaluation metric (geometry.py:754-896): all-pairs distances on the Steiner-point graph of the mesh
+# ----------------------------------------------------------------------------------------------
+def _as_numpy(x):
+    """torch tensor (any device) or array-like -> numpy array on the host."""
+    import numpy as np
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _steiner_graph(verts, faces, n_steiner):
+    """``mesh_distance_graph`` and the [n_nodes, 3] fp64 positions of its nodes."""
+    import numpy as np
+    import scipy.sparse
+    x = np.asarray(_as_numpy(verts), dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(_as_numpy(faces)).astype(np.int64).reshape(-1, 3)
+    V, m = x.shape[0], int(n_steiner)
+    if m < 0:
+        raise ValueError("n_steiner must be >= 0")
+    if f.size and (f.min() < 0 or f.max() >= V):
+        raise ValueError("mesh_distance_graph: a face index is outside [0, %d)" % V)
+    # half-edge i of a face runs f[i] -> f[i + 1] and faces the vertex f[i + 2]
+    ha, hb, opp = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1), f[:, [2, 0, 1]].reshape(-1)
+    key = np.minimum(ha, hb) * V + np.maximum(ha, hb)
+    ukey, edge_of = np.unique(key, return_inverse=True)
+    ea, eb = ukey // V, ukey % V
+    E = ukey.shape[0]
+    t = (np.arange(1, m + 1, dtype=np.float64) / (m + 1))[None, :, None]
+    pos = np.concatenate([x, ((1.0 - t) * x[ea][:, None, :] + t * x[eb][:, None, :]).reshape(-1, 3)])
+    steiner = V + np.arange(E, dtype=np.int64)[:, None] * m + np.arange(m, dtype=np.int64)[None, :]          # [E, m]
+    chain = np.concatenate([ea[:, None], steiner, eb[:, None]], axis=1)                                    # (i)
+    tails, tips = [chain[:, :-1].reshape(-1)], [chain[:, 1:].reshape(-1)]
+    if m:
+        fs = steiner[edge_of].reshape(-1, 3, m)                                                            # the Steiner nodes of a face's edges
+        for p, q in ((0, 1), (1, 2), (0, 2)):                                                              # (ii)
+            tails.append(np.repeat(fs[:, p, :], m, axis=1).reshape(-1))
+            tips.append(np.tile(fs[:, q, :], (1, m)).reshape(-1))
+        tails.append(steiner[edge_of].reshape(-1))                                                         # (iii)
+        tips.append(np.repeat(opp, m))
+    tail, tip = np.concatenate(tails), np.concatenate(tips)
+    n = pos.shape[0]
+    lo, hi = np.minimum(tail, tip), np.maximum(tail, tip)
+    pair = np.unique(lo[lo != hi] * n + hi[lo != hi])                                                      # each arc once
+    lo, hi = pair // n, pair % n
+    w = np.sqrt(((pos[lo] - pos[hi]) ** 2).sum(axis=1))
+    g = scipy.sparse.coo_matrix((np.concatenate([w, w]), (np.concatenate([lo, hi]), np.concatenate([hi, lo]))), shape=(n, n)).tocsr()
+    g.sort_indices()
+    return g, pos
+
+
+def mesh_distance_graph(verts, faces, n_steiner=3):
+    """The Steiner-point graph of a triangle mesh (Lanthier, Maheshwari, Sack) as a symmetric scipy CSR matrix of fp64 arc lengths.
+
+    Nodes 0 .. V-1 are the vertices (positions cast to fp64).  Every undirected edge (a, b), a < b, that occurs in a face carries
+    ``m = n_steiner`` further nodes at (1 - t) x_a + t x_b, t = j / (m + 1), j = 1 .. m; edge e (edges sorted by (a, b)) owns nodes
+    V + e m .. V + e m + m - 1.  Arcs, each once, weighted by the Euclidean distance of the two node positions: (i) consecutive nodes
+    along every edge, a, s_1, .., s_m, b; (ii) in every face, every Steiner node with every Steiner node of the face's other two edges;
+    (iii) in every face, every Steiner node with the vertex opposite its edge.  Every arc is a straight segment inside a face, so a path of
+    the graph is a path on the surface: graph distances are never below the geodesic, exact along edges, and can only fall as m grows.
+    ``n_steiner = 0`` is the edge graph.  Boundary and non-manifold edges, duplicate vertices (zero-length arcs) and unreferenced
+    vertices (empty rows) are legal.  Vectorised numpy: no Python loop over faces or edges."""
+    return _steiner_graph(verts, faces, n_steiner)[0]
+
+
+def _geodesic_on_device():
+    return torch.cuda.is_available() or ops._hip._allow_host_tensors
+
+
+_GEODESIC_BLOCK_BYTES = 1 << 30
+
+
+def geodesic_distances(verts, faces, sources=None, n_steiner=3):
+    """Distances on the surface from the vertices ``sources`` (None: all) to every vertex: [len(sources), V] fp64 numpy, torch or numpy in.
+    Shortest paths on ``mesh_distance_graph(verts, faces, n_steiner)``: an upper bound of the geodesic distance, exact along edges.
+    With a ROCm device the (min, +) sweeps of ``ops.minplus_distances`` (dn_geodesic.hip), otherwise ``scipy.sparse.csgraph.dijkstra`` on
+    the same graph; both return, for every pair, the minimum over paths of the left-to-right fp64 sum of the arc lengths -- the same bits."""
+    import numpy as np
+    g = mesh_distance_graph(verts, faces, n_steiner)
+    V = np.asarray(_as_numpy(verts)).reshape(-1, 3).shape[0]
+    src = np.arange(V, dtype=np.int64) if sources is None else np.asarray(_as_numpy(sources)).astype(np.int64).reshape(-1)
+    if src.size and (src.min() < 0 or src.max() >= V):
+        raise ValueError("geodesic_distances: a source is outside [0, %d)" % V)
+    out = np.empty((src.shape[0], V), dtype=np.float64)
+    if src.size == 0 or V == 0:
+        return out
+    if not _geodesic_on_device():
+        import scipy.sparse.csgraph
+        out[:] = scipy.sparse.csgraph.dijkstra(g, directed=True, indices=src)[:, :V]
+        return out
+    # (host buffers only while the test suite has bound the emulator build of the library, which cannot read device memory)
+    dev = torch.device("cpu") if ops._hip._allow_host_tensors else torch.device("cuda", torch.cuda.current_device())
+    gd, new_of = _band_ordered(g)
+    rowptr = torch.from_numpy(gd.indptr.astype(np.int32)).to(dev)
+    col = torch.from_numpy(gd.indices.astype(np.int32)).to(dev)
+    w = torch.from_numpy(gd.data.astype(np.float64)).to(dev)
+    keep = torch.from_numpy(new_of[:V]).to(dev)
+    n = g.shape[0]
+    per_call = max(1, _GEODESIC_BLOCK_BYTES // (8 * n))          # only the V vertex columns of a block are kept: bounded device memory
+    for s0 in range(0, src.shape[0], per_call):
+        d = ops.minplus_distances(rowptr, col, w, torch.from_numpy(new_of[src[s0:s0 + per_call]]), max_block_bytes=_GEODESIC_BLOCK_BYTES)
+        out[s0:s0 + d.shape[0]] = d[:, keep].cpu().numpy()
+    return out
+
+
+def _band_ordered(g):
+    """``g`` with its nodes renumbered in reverse Cuthill-McKee order, and ``new_of`` [n] int64 (new number of every old node).  The
+    kernel's workgroups own runs of consecutive nodes, so neighbours numbered close to each other are rows that are still in cache; a
+    distance is a minimum over paths and does not depend on how the nodes are numbered, so the result is the same bits."""
+    import numpy as np
+    import scipy.sparse
+    import scipy.sparse.csgraph
+    n = g.shape[0]
+    old_of = scipy.sparse.csgraph.reverse_cuthill_mckee(g, symmetric_mode=True).astype(np.int64)
+    new_of = np.empty(n, dtype=np.int64)
+    new_of[old_of] = np.arange(n, dtype=np.int64)
+    coo = g.tocoo()
+    gd = scipy.sparse.coo_matrix((coo.data, (new_of[coo.row], new_of[coo.col])), shape=(n, n)).tocsr()   # (explicit zeros stay arcs)
+    gd.sort_indices()
+    return gd, new_of
+
+
+def _geodesic_cache_lookup(cache_dir, stem, verts_np, faces_np):
+    """The reference's bucket search (geometry.py:824-850) over ``<stem>_<i>.npz``: (matrix or None, the path of the first free bucket)."""
+    import os
+    import numpy as np
+    i = 0
+    while True:
+        path = os.path.join(cache_dir, "%s_%d.npz" % (stem, i))
+        try:
+            npz = np.load(path, allow_pickle=True)
+        except FileNotFoundError:
+            return None, path
+        if np.array_equal(verts_np, npz["verts"]) and np.array_equal(faces_np, npz["faces"]):
+            return npz["dist"], path
+        i += 1
+
+
+def _symmetrised(dists):
+    """geometry.py:871-879: non-finite -> NaN, fmin with the transpose, what is still NaN -> the largest finite value."""
+    import numpy as np
+    dists = np.nan_to_num(dists, nan=np.nan, posinf=np.nan, neginf=np.nan)
+    dists = np.fmin(dists, np.transpose(dists))
+    max_dist = np.nanmax(dists)
+    return np.nan_to_num(dists, nan=max_dist, posinf=max_dist, neginf=max_dist)
+
+
+def get_all_pairs_geodesic_distance(verts_np, faces_np, geodesic_cache_dir=None, *, method="steiner", n_steiner=3):
+    """The dense V x V matrix of surface distances (geometry.py:804-896; numpy in, numpy out), cached as the reference caches it.
+
+    ``method='steiner'`` (default): ``geodesic_distances`` on the Steiner-point graph with ``n_steiner`` nodes per edge -- an upper bound
+    of the geodesic, where the reference is exact.  ``method='exact'``: ``igl.exact_geodesic`` per source, as the reference does (needs
+    libigl).  Either way the matrix is made exactly symmetric as in the reference.
+
+    Cache: a file in the reference's own format and name, ``<hash>_<i>.npz`` (keys verts, faces, dist), was written by libigl, is exact,
+    and is returned as it is whatever ``method`` says.  Only ``method='exact'`` writes under that name; the Steiner route reads and writes
+    ``<hash>_steiner<m>_<i>.npz`` (the same keys plus method and n_steiner)."""
+    import numpy as np
+    from . import utils
+    if method not in ("steiner", "exact"):
+        raise ValueError("unrecognized method")
+    m = int(n_steiner)
+    exact_path = own_path = None
+    if geodesic_cache_dir is not None:
+        utils.ensure_dir_exists(geodesic_cache_dir)
+        key = str(utils.hash_arrays((verts_np, faces_np)))
+        found, exact_path = _geodesic_cache_lookup(geodesic_cache_dir, key, verts_np, faces_np)
+        if found is not None:
+            return found
+        if method == "steiner":
+            found, own_path = _geodesic_cache_lookup(geodesic_cache_dir, "%s_steiner%d" % (key, m), verts_np, faces_np)
+            if found is not None:
+                return found
+    if method == "exact":
+        try:
+            import igl
+        except ImportError:
+            raise ImportError("method='exact' needs python libigl (`conda install -c conda-forge igl`); "
+                              "method='steiner' computes an upper bound of the geodesic distances without it")
+        print("Computing all-pairs geodesic distance (method=exact, igl.exact_geodesic per source; warning: SLOW!)")
+        N = verts_np.shape[0]
+        targets = np.arange(N)[:, np.newaxis]
+        dists = np.array([igl.exact_geodesic(verts_np, faces_np, np.array([i])[:, np.newaxis], targets) for i in range(N)])
+        dists = _symmetrised(dists.reshape(N, N))
+        if exact_path is not None:
+            np.savez(exact_path, verts=verts_np, faces=faces_np, dist=dists)
+        return dists
+    print("Computing all-pairs geodesic distance (method=steiner, n_steiner=%d)" % m)
+    dists = _symmetrised(geodesic_distances(verts_np, faces_np, None, m))
+    if own_path is not None:
+        np.savez(own_path, verts=verts_np, faces=faces_np, dist=dists, method="steiner", n_steiner=m)
+    return dists
+
+
+def geodesic_label_errors(target_verts, target_faces, pred_labels, gt_labels, normalization='diameter', geodesic_cache_dir=None):
+    """Distances on the target surface between predicted and ground-truth labels (geometry.py:754-781), divided by the largest distance of
+    the surface (``'diameter'``: a numpy array) or by the square root of its area (``'area'``: an fp64 torch tensor, as in the reference).
+    The distances are ``get_all_pairs_geodesic_distance``'s: exact where the cache holds a matrix libigl wrote, otherwise the Steiner-graph
+    upper bound."""
+    import numpy as np
+    if normalization not in ("diameter", "area"):
+        raise ValueError("unrecognized normalization")
+    target_verts, target_faces = _as_numpy(target_verts), _as_numpy(target_faces)
+    pred_labels, gt_labels = _as_numpy(pred_labels), _as_numpy(gt_labels)
+    dists = get_all_pairs_geodesic_distance(target_verts, target_faces, geodesic_cache_dir)
+    result_dists = dists[pred_labels, gt_labels]
+    if normalization == "diameter":
+        return result_dists / np.max(dists)
+    v, f = torch.tensor(target_verts), torch.tensor(target_faces).long()
+    coords = v[f]
+    total_area = torch.sum(0.5 * torch.linalg.cross(coords[:, 1] - coords[:, 0], coords[:, 2] - coords[:, 0], dim=-1).norm(dim=-1))
+    return torch.as_tensor(result_dists) / torch.sqrt(total_area)

@@ -313,6 +313,79 @@ def cloud_operators(points, nbr, normals=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# all-pairs graph distances: (min, +) relaxation sweeps (include/diffnet_hip.h: dn_minplus_sweeps_f64)
+# ----------------------------------------------------------------------------------------------
+@_on_device
+def _minplus_block(rowptr, col, w, src, n_nodes, sweeps_per_check):
+    """Distances [n_nodes, len(src)] (node-major) from the nodes ``src`` (int64, on the graph's device): swept in groups of
+    ``sweeps_per_check`` until a group's last sweep lowers nothing."""
+    L = _hip.lib()
+    dev = w.device
+    S = src.numel()
+    dist = torch.full((n_nodes, S), float("inf"), dtype=torch.float64, device=dev)
+    dist[src, torch.arange(S, device=dev)] = 0.0
+    changed = torch.zeros(1, dtype=torch.int32, device=dev)
+    done = 0
+    while True:
+        n = min(sweeps_per_check, n_nodes - done)
+        if n <= 0:
+            raise RuntimeError("minplus_distances: no fixed point after %d sweeps of %d nodes" % (done, n_nodes))
+        _hip.check(L.dn_minplus_sweeps_f64(rowptr.data_ptr(), col.data_ptr(), w.data_ptr(), n_nodes, dist.data_ptr(), S, n, changed.data_ptr(),
+                                           _hip.stream_of(w)), "dn_minplus_sweeps_f64")
+        done += n
+        if not int(changed.item()):          # the one host read per group of sweeps
+            return dist
+
+
+def minplus_distances(rowptr, col, w, sources, *, sweeps_per_check=8, max_block_bytes=1 << 30):
+    """Shortest-path distances on a graph by (min, +) relaxation sweeps (dn_geodesic.hip), forward only.  ``rowptr`` [n_nodes + 1] and
+    ``col`` [nnz] int32: CSR arcs; ``w`` [nnz] fp64 arc lengths, non-negative; ``sources`` int64 node indices (duplicates allowed).
+    -> [len(sources), n_nodes] fp64 on the graph's device, ``inf`` where no path exists: for every pair the minimum over paths of the
+    left-to-right fp64 sum of the arc lengths -- the bits ``scipy.sparse.csgraph.dijkstra`` returns.
+
+    The sources are cut into blocks whose node-major distance block fits ``max_block_bytes``; a block is swept ``sweeps_per_check`` sweeps
+    at a time and the device's changed word read after each group (this op synchronises with the host by design: it is evaluation code).
+    ``ValueError`` before any launch for a negative or NaN length and for a column or source outside [0, n_nodes); ``RuntimeError`` if
+    n_nodes sweeps reach no fixed point (impossible with non-negative lengths)."""
+    for t in (rowptr, col, w):
+        _hip.require_device(t)
+    if rowptr.dtype != torch.int32 or col.dtype != torch.int32:
+        raise TypeError("minplus_distances takes int32 rowptr and col (got %s, %s)" % (rowptr.dtype, col.dtype))
+    if w.dtype != torch.float64:
+        raise TypeError("minplus_distances takes fp64 arc lengths (got %s)" % w.dtype)
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1 or w.dim() != 1 or col.numel() != w.numel():
+        raise ValueError("minplus_distances takes CSR arrays rowptr [n + 1], col [nnz], w [nnz]")
+    if not (rowptr.device == col.device == w.device):
+        raise RuntimeError("minplus_distances: the CSR arrays are on %s, %s and %s" % (rowptr.device, col.device, w.device))
+    dev = w.device
+    rowptr, col, w = rowptr.contiguous(), col.contiguous(), w.contiguous()
+    n_nodes, nnz = rowptr.numel() - 1, col.numel()
+    sources = torch.as_tensor(sources, dtype=torch.int64).reshape(-1).to(dev)
+    sweeps_per_check, max_block_bytes = int(sweeps_per_check), int(max_block_bytes)
+    if sweeps_per_check < 1:
+        raise ValueError("sweeps_per_check must be >= 1")
+    rp = rowptr.to(torch.int64)
+    if int(rp[0]) != 0 or int(rp[-1]) != nnz or (n_nodes and bool((rp[1:] < rp[:-1]).any())):
+        raise ValueError("minplus_distances: rowptr is not a non-decreasing row pointer of %d entries" % nnz)
+    if nnz:
+        if bool(torch.isnan(w).any()) or bool((w < 0).any()):
+            raise ValueError("minplus_distances takes non-negative arc lengths (negative or NaN found)")
+        if int(col.min()) < 0 or int(col.max()) >= n_nodes:
+            raise ValueError("minplus_distances: a column index is outside [0, %d)" % n_nodes)
+    if sources.numel() and (int(sources.min()) < 0 or int(sources.max()) >= n_nodes):
+        raise ValueError("minplus_distances: a source is outside [0, %d)" % n_nodes)
+    S = sources.numel()
+    out = torch.empty(S, n_nodes, dtype=torch.float64, device=dev)
+    if S == 0 or n_nodes == 0:
+        return out
+    per_block = max(1, min(S, max_block_bytes // (8 * n_nodes), 65535 * 64))
+    for s0 in range(0, S, per_block):
+        src = sources[s0:s0 + per_block]
+        out[s0:s0 + src.numel()] = _minplus_block(rowptr, col, w, src, n_nodes, sweeps_per_check).t()
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # functional maps: the regularised spectral solve (include/diffnet_hip.h: dn_fmap_solve_*_f32)
 # ----------------------------------------------------------------------------------------------
 def _fmap_ws(A):

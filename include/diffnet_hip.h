@@ -388,6 +388,24 @@ int dn_fmap_solve_fwd_f32(const float* A, const float* B, const float* evals_x, 
 int dn_fmap_solve_bwd_f32(const float* A, const float* B, const float* evals_x, const float* evals_y, const float* dC, int P, int K, int F, float lam,
                           float* dA, float* dB, void* ws, size_t ws_bytes, int32_t* status, void* stream);
 
+/* ---- all-pairs mesh distances (geometry.geodesic_label_errors, geometry.py:754-896): (min, +) relaxation sweeps of a block of distance
+ *      columns over a graph (dn_geodesic.hip).  rowptr [n_nodes + 1], col [nnz] int32: the CSR arcs of every node, columns in [0, n_nodes)
+ *      (NOT checked here: the caller validates them); w [nnz] fp64 arc lengths, non-negative and not NaN.  dist [n_nodes, n_src] fp64,
+ *      NODE-major: column s holds the distances from source s, which the caller initialises (inf, 0 at the source).  One sweep is
+ *          dist[v][s] = min(dist[v][s], dist[u][s] + w)   over every arc (u, w) of row v, every v and every s,
+ *      one fp64 add per arc and nothing reassociated.  The call runs n_sweeps sweeps IN PLACE, one launch each: values only decrease and
+ *      each is the length of a path, so the fixed point -- the minimum over paths of the left-to-right fp64 sum, what Dijkstra returns --
+ *      does not depend on the order in which lanes see each other's stores; how many sweeps reach it may.  Any n_src (lanes are masked,
+ *      nothing is padded), any n_nodes, empty rows and rows of any length are handled.
+ *      changed: one device int32 that the call first sets to 0 and then sets to 1 if its LAST sweep lowered any value; 0 after a call with
+ *      n_sweeps >= 1 therefore certifies the fixed point.  The caller reads it at its next synchronisation point.
+ *      No workspace, no allocation, no synchronisation.  dn_minplus_node_tile(): the nodes a workgroup owns (for tests of ragged sizes).
+ *      Returns 0 on success (n_nodes, n_src or n_sweeps == 0: only the word is cleared) and non-zero WITHOUT launching for a negative
+ *      count, a NULL changed, a NULL rowptr or dist otherwise, or n_src > 65535 * 64. */
+int dn_minplus_node_tile(void);
+int dn_minplus_sweeps_f64(const int32_t* rowptr, const int32_t* col, const double* w, int n_nodes, double* dist, int n_src, int n_sweeps,
+                          int32_t* changed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

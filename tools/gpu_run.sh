@@ -12,6 +12,8 @@
 #   cloud        ops.knn and the point-cloud pass dn_cloud_operators_f32 at 10 000 and 200 000 points, host route at 10 000 (tools/cloud_timing.py)
 #   fmap         one forward + backward step of the functional map at the functional_correspondence shape: HIP route, torch route and the
 #                script's row loop of torch.inverse, with launches per step (tools/fmap_timing.py)
+#   geodesic     all-pairs mesh distances at the FAUST size for n_steiner = 0, 1, 3: sweeps, time of a sweep and of the device route, scipy's
+#                Dijkstra scaled from 64 sources; the accuracy tables of the Steiner graph on the CPU route (tools/geodesic_timing.py)
 #   tests [k]    GPU parity tier (optionally -k <expr>)
 #   bench [args] bench.py (default flags: the timed steps only; add --full for the rest) -> $DN_OUT_DIR/bench.json
 #   prof         rocprofv3 --kernel-trace --stats of bench.py --full -> $DN_OUT_DIR/prof/
@@ -70,6 +72,8 @@ cloud)
   timeout 300 python tools/cloud_timing.py ;;
 fmap)
   timeout 300 python tools/fmap_timing.py ;;
+geodesic)
+  timeout 900 python tools/geodesic_timing.py "$@" ;;
 tests)
   if [ -n "$1" ]; then timeout 1500 python -m pytest tests/test_gpu_parity.py -m gpu -q --tb=short -x -k "$1" 2>&1 | tail -40 | tee $OUT/tests.txt
   else timeout 2400 python -m pytest tests -m gpu -q --tb=short -x 2>&1 | tail -40 | tee $OUT/tests.txt; fi ;;
