@@ -6,7 +6,8 @@ The host-side operator precompute keeps the reference's names here (``compute_op
 ``get_all_operators``, ``normalize_positions``, ``compute_hks[_autoscale]``) and lives in ``precompute.py``
 (numpy/scipy restatement).  ``find_knn`` is the nearest-neighbour query of the evaluation scripts and of the
 point-cloud operators: ``vertex_normals``, ``build_tangent_frames``, ``build_grad_point_cloud`` (the reference's names) and
-``cloud_operators`` (normals, frames and gradient stencils of a cloud in one HIP pass over its neighbour table).
+``cloud_operators`` (normals, frames and gradient stencils of a cloud in one HIP pass over its neighbour table);
+``point_cloud_laplacian`` is the local-Delaunay Laplacian and mass of a cloud (dn_cloud_lap.hip on the device).
 ``geodesic_label_errors`` and ``get_all_pairs_geodesic_distance`` are the evaluation metric of the correspondence experiments: all-pairs
 distances on the mesh's Steiner-point graph (``mesh_distance_graph``, ``geodesic_distances``), swept on the device by dn_geodesic.hip.
 """
@@ -208,9 +209,14 @@ def build_grad_point_cloud(verts, frames, n_neighbors_cloud=30):
     least-squares stencil over the edges to the ``n_neighbors_cloud`` nearest neighbours of i, real part X, imaginary part Y.  The
     result lives on the host, so only the neighbour query runs on the device (``find_knn``); the tangent coordinates are formed in the
     dtype of ``verts`` and the 2 x 2 systems solved in fp64, both as in the reference."""
+    nbr = find_knn(verts, verts, int(n_neighbors_cloud), omit_diagonal=True, method="cpu_kd").indices
+    return _grad_of_table(verts, frames, nbr)
+
+
+def _grad_of_table(verts, frames, nbr):
+    """``build_grad_point_cloud`` on a given neighbour table [V, k] (int64, on the device of ``verts``)."""
     import numpy as np
-    V, k = verts.shape[0], int(n_neighbors_cloud)
-    nbr = find_knn(verts, verts, k, omit_diagonal=True, method="cpu_kd").indices
+    V, k = nbr.shape
     tail = torch.arange(V, device=verts.device).repeat_interleave(k)
     tip = nbr.reshape(-1)
     frames = frames.to(device=verts.device, dtype=verts.dtype)
@@ -230,6 +236,11 @@ def cloud_operators(verts, n_neighbors_cloud=30, normals=None):
     and never touch the host: fp64 inside, normals signed as include/diffnet_hip.h defines.  Everything else (host tensors, fp64, larger
     neighbourhoods) takes the reference's arithmetic in vectorised numpy: ``find_knn`` (``cpu_kd``), batched SVD in the dtype of
     ``verts`` with LAPACK's sign, frames in that dtype, 2 x 2 systems in fp64."""
+    return _cloud_operators_and_table(verts, n_neighbors_cloud, normals)[:3]
+
+
+def _cloud_operators_and_table(verts, n_neighbors_cloud, normals):
+    """``cloud_operators`` and the neighbour table [V, k] (int64, on the device of ``verts``) its gradient operator was built from."""
     V = verts.shape[0]
     if _cloud_on_device(verts, n_neighbors_cloud):
         k = int(n_neighbors_cloud)
@@ -240,14 +251,48 @@ def cloud_operators(verts, n_neighbors_cloud=30, normals=None):
         idx = torch.stack((torch.arange(V, device=verts.device).repeat_interleave(k + 1), col.to(torch.int64)))
         gradX = torch.sparse_coo_tensor(idx, vx, (V, V)).coalesce()
         gradY = torch.sparse_coo_tensor(idx, vy, (V, V)).coalesce()
-        return frames, gradX, gradY
+        return frames, gradX, gradY, nbr
+    nbr = find_knn(verts, verts, int(n_neighbors_cloud), omit_diagonal=True, method="cpu_kd").indices
     if normals is None:
-        normals = _cloud_normals_host(verts, n_neighbors_cloud)
+        v = verts.detach().cpu().numpy()
+        normals = torch.from_numpy(neighborhood_normal(v[nbr.cpu().numpy()] - v[:, None, :])).to(device=verts.device, dtype=verts.dtype)
         if torch.any(torch.isnan(normals)):
             raise ValueError("NaN normals :(")
     frames = _frames_of_normals(normals.to(device=verts.device, dtype=verts.dtype))
-    grad = build_grad_point_cloud(verts, frames, n_neighbors_cloud)
-    return (frames, _pre._to_torch_sparse(grad.real, verts.device, verts.dtype), _pre._to_torch_sparse(grad.imag, verts.device, verts.dtype))
+    grad = _grad_of_table(verts, frames, nbr)
+    return (frames, _pre._to_torch_sparse(grad.real, verts.device, verts.dtype), _pre._to_torch_sparse(grad.imag, verts.device, verts.dtype), nbr)
+
+
+def _laplacian_of_table(verts, nbr, frames):
+    """(L coalesced sparse COO [V,V], mass [V]) of the local-Delaunay construction on a neighbour table and frames, on the device and in
+    the dtype of ``verts``: ``ops.cloud_laplacian`` where ``cloud_operators`` runs its kernels, otherwise the numpy route in fp64."""
+    V = verts.shape[0]
+    if _cloud_on_device(verts, nbr.shape[1]):
+        _, rowptr, col, val, mass = ops.cloud_laplacian(verts, nbr, frames.to(device=verts.device, dtype=torch.float32))
+        counts = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(V, device=verts.device), counts, output_size=col.numel())
+        return torch.sparse_coo_tensor(torch.stack((rows, col.to(torch.int64))), val, (V, V)).coalesce(), mass
+    L, mass = _pre.point_cloud_laplacian_from_table(verts.detach().cpu().numpy(), nbr.detach().cpu().numpy(), frames.detach().cpu().numpy())
+    return _pre._to_torch_sparse(L, verts.device, verts.dtype), torch.from_numpy(mass).to(device=verts.device, dtype=verts.dtype)
+
+
+def point_cloud_laplacian(verts, n_neighbors=30, frames=None):
+    """Laplacian and lumped mass of a point cloud: ``(L, massvec)``, L a coalesced sparse COO [V,V], both on the device and in the dtype
+    of ``verts``.  The local-Delaunay construction of Sharp & Crane (2020, section 5.7) as ``precompute.point_cloud_laplacian_host``
+    states it -- NOT robust_laplacian's, which re-triangulates the same triangles intrinsically (tufted cover): here single weights can be
+    negative on bad samplings, while L is symmetric, has zero row sums and is positive semi-definite regardless.  ``frames`` [V,3,3]: use
+    these tangent frames instead of those of the estimated normals.
+
+    fp32 points on a ROCm device with ``n_neighbors <= 32`` run ``ops.knn``, ``ops.cloud_operators`` (skipped when ``frames`` is given)
+    and ``ops.cloud_laplacian`` (dn_knn.hip, dn_cloud.hip, dn_cloud_lap.hip) and never touch the host; everything else takes
+    ``precompute.point_cloud_laplacian_host`` (vectorised numpy in fp64)."""
+    if _cloud_on_device(verts, n_neighbors):
+        nbr = ops.knn(verts, verts, int(n_neighbors), omit_diagonal=True)[1]
+        if frames is None:
+            frames = ops.cloud_operators(verts, nbr)[1]
+        return _laplacian_of_table(verts, nbr, frames)
+    L, mass = _pre.point_cloud_laplacian_host(verts.detach().cpu().numpy(), n_neighbors, frames)
+    return _pre._to_torch_sparse(L, verts.device, verts.dtype), torch.from_numpy(mass).to(device=verts.device, dtype=verts.dtype)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -312,6 +312,82 @@ def cloud_operators(points, nbr, normals=None):
     return tuple(out)
 
 
+@_on_device
+def _cloud_laplacian_launch(points, nbr, frames):
+    """Every device step of ``cloud_laplacian`` without a host read: star, emit, stable sort of the keys (torch), segment sums.
+    -> (partner [N, k] int32, rowptr [N + 1] int32, col, val [9 N k] (the first ``count`` entries are the matrix), mass [N] fp32,
+    count [1] int32, status [1] int32)."""
+    L = _hip.lib()
+    n, k = nbr.shape
+    dev = points.device
+    slots = n * k
+    m = 9 * slots
+    st = _hip.stream_of(points)
+    partner = torch.empty(n, k, dtype=torch.int32, device=dev)
+    rowptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    val = torch.empty(max(m, 1), dtype=torch.float32, device=dev)
+    mass = torch.zeros(n, dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return partner, rowptr, col[:0], val[:0], mass, count, status
+    _hip.check(L.dn_cloud_star_f32(points.data_ptr(), n, nbr.data_ptr(), k, frames.data_ptr(), partner.data_ptr(), status.data_ptr(), st),
+               "dn_cloud_star_f32")
+    nbytes = L.dn_cloud_laplacian_workspace_bytes(n, k)
+    ws = _hip.workspace(dev, nbytes)
+    _hip.check(L.dn_cloud_laplacian_emit_f32(points.data_ptr(), n, nbr.data_ptr(), k, partner.data_ptr(), ws.data_ptr(), ws.numel(), st),
+               "dn_cloud_laplacian_emit_f32")
+    # the workspace layout of include/diffnet_hip.h
+    key_l, val_l = ws[:72 * slots].view(torch.int64), ws[72 * slots:144 * slots].view(torch.float64)
+    key_m, val_m = ws[144 * slots:168 * slots].view(torch.int64), ws[168 * slots:192 * slots].view(torch.float64)
+    skey, perm = torch.sort(key_l, stable=True)
+    head = torch.ones(m, dtype=torch.bool, device=dev)
+    torch.ne(skey[1:], skey[:-1], out=head[1:])
+    rank = torch.cumsum(head, 0, dtype=torch.int64)
+    _hip.check(L.dn_segment_sum_f64_f32(skey.data_ptr(), perm.data_ptr(), val_l.data_ptr(), m, rank.data_ptr(), n, rowptr.data_ptr(),
+                                        col.data_ptr(), val.data_ptr(), count.data_ptr(), st), "dn_segment_sum_f64_f32")
+    skey_m, perm_m = torch.sort(key_m, stable=True)
+    _hip.check(L.dn_segment_sum_f64_f32(skey_m.data_ptr(), perm_m.data_ptr(), val_m.data_ptr(), 3 * slots, None, n, None, None,
+                                        mass.data_ptr(), None, st), "dn_segment_sum_f64_f32")
+    return partner, rowptr, col, val, mass, count, status
+
+
+def cloud_laplacian(points, nbr, frames):
+    """Laplacian and lumped mass of a point cloud from the local Delaunay star of every point among its projected neighbours (Sharp &
+    Crane 2020, section 5.7, without the intrinsic / tufted re-triangulation; include/diffnet_hip.h: dn_cloud_star_f32), forward only.
+    ``points`` [N, 3] fp32, ``nbr`` [N, k] int64 as ``ops.knn(points, points, k, omit_diagonal=True)`` returns them, ``frames`` [N, 3, 3]
+    fp32 as ``ops.cloud_operators`` returns them (rows basisX, basisY are read).
+    -> (partner [N, k] int32, rowptr [N + 1] int32, col [nnz] int32, val [nnz] fp32, mass [N] fp32): ``partner[i, a]`` is the slot b of the
+    triangle (i, nbr[i, a], nbr[i, b]) of the star of i, or -1; L is CSR with ascending columns, symmetric bit for bit, and repeats bit for
+    bit from call to call.  Raises ``IndexError`` if a row of ``nbr`` holds an index outside [0, N) (reading the status word and the
+    number of entries waits for the kernels)."""
+    _hip.require_device(points)
+    _hip.require_device(nbr)
+    _hip.require_device(frames)
+    points, frames = _f32c(points), _f32c(frames)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("cloud_laplacian takes [N, 3] points (got %s)" % (tuple(points.shape),))
+    if nbr.dim() != 2 or nbr.shape[0] != points.shape[0]:
+        raise ValueError("cloud_laplacian takes [N, k] neighbour indices for [N, 3] points (got %s for %s)" % (tuple(nbr.shape), tuple(points.shape)))
+    if nbr.dtype != torch.int64:
+        raise TypeError("cloud_laplacian takes int64 neighbour indices (got %s)" % nbr.dtype)
+    n, k = nbr.shape
+    if tuple(frames.shape) != (n, 3, 3):
+        raise ValueError("cloud_laplacian takes [N, 3, 3] frames (got %s)" % (tuple(frames.shape),))
+    if nbr.device != points.device or frames.device != points.device:
+        raise RuntimeError("cloud_laplacian: points on %s, neighbour indices on %s, frames on %s" % (points.device, nbr.device, frames.device))
+    if not 1 <= k <= _hip.KNN_MAX_K:
+        raise ValueError("cloud_laplacian kernel takes 1 <= k <= %d neighbours (got %d)" % (_hip.KNN_MAX_K, k))
+    if 9 * n * k > 2 ** 31 - 1:
+        raise ValueError("cloud_laplacian: 9 x %d x %d matrix terms do not fit a 32-bit count" % (n, k))
+    partner, rowptr, col, val, mass, count, status = _cloud_laplacian_launch(points, nbr.contiguous(), frames)
+    bad, nnz = torch.cat((status, count)).tolist()
+    if bad:
+        raise IndexError("cloud_laplacian: %d row(s) of the neighbour table hold an index outside [0, %d)" % (bad, n))
+    return partner, rowptr, col[:nnz].clone(), val[:nnz].clone(), mass
+
+
 # ----------------------------------------------------------------------------------------------
 # all-pairs graph distances: (min, +) relaxation sweeps (include/diffnet_hip.h: dn_minplus_sweeps_f64)
 # ----------------------------------------------------------------------------------------------

@@ -11,8 +11,9 @@ numpy/scipy only, fully vectorised:
 and the npz operator cache of ``get_operators`` (geometry.py:426-570) with the same file naming
 (sha1(verts,faces)_<bucket>.npz) and the same keys, so caches written by either implementation are interchangeable.
 Point clouds (empty ``faces``): normals, frames and gradients come from ``geometry.cloud_operators`` (HIP kernel on a ROCm device,
-vectorised numpy otherwise); only the point-cloud LAPLACIAN of robust_laplacian is not restated -- ``compute_operators`` takes it from
-its ``laplacian=`` argument or from that package if it is installed.
+vectorised numpy otherwise); the point-cloud LAPLACIAN of robust_laplacian is not restated -- ``compute_operators`` takes it from its
+``laplacian=`` argument or from that package if it is installed -- but ``laplacian="delaunay"`` builds the local-Delaunay Laplacian the
+wheel starts from (``point_cloud_laplacian_host`` here, dn_cloud_lap.hip on a ROCm device), without its intrinsic re-triangulation.
 """
 from __future__ import annotations
 
@@ -161,6 +162,133 @@ def laplacian_eigenbasis(L: sp.spmatrix, massvec: np.ndarray, k_eig: int):
             A = A + sp.identity(L.shape[0]) * (EPS * 10 ** fails)
 
 
+# ----------------------------------------------------------------------------------------- point-cloud Laplacian (local Delaunay stars)
+STAR_CR_TOL = 1e-12   # |cross(a, b)| <= STAR_CR_TOL sqrt(W_a W_b): a, b and the centre are collinear (dn_cloud_lap.hip: LP_CR_TOL)
+
+
+def cloud_project(pts: np.ndarray, nbr: np.ndarray, frames: np.ndarray):
+    """Tangent-plane coordinates of every neighbour about its point: X, Y, W = X^2 + Y^2, each [V, k] fp64.  A slot whose index is the
+    point itself, or that projects onto it, has W = 0 and takes no part in the star."""
+    pts, frames = np.asarray(pts, dtype=np.float64), np.asarray(frames, dtype=np.float64).reshape(-1, 3, 3)
+    e = pts[nbr] - pts[:, None, :]
+    X = np.einsum("nkd,nd->nk", e, frames[:, 0])
+    Y = np.einsum("nkd,nd->nk", e, frames[:, 1])
+    own = nbr == np.arange(pts.shape[0])[:, None]
+    X, Y = np.where(own, 0.0, X), np.where(own, 0.0, Y)
+    W = X * X + Y * Y
+    dead = ~(W > 0)
+    return np.where(dead, 0.0, X), np.where(dead, 0.0, Y), np.where(dead, 0.0, W)
+
+
+def _incircle(xa, ya, wa, xb, yb, wb, cr_ab, xc, yc, wc):
+    """< 0: c strictly inside circle(0, a, b) for (a, b) counter-clockwise (cr_ab > 0)."""
+    return wc * cr_ab - wb * (xa * yc - ya * xc) + wa * (xb * yc - yb * xc)
+
+
+def cloud_stars(X: np.ndarray, Y: np.ndarray, W: np.ndarray) -> np.ndarray:
+    """partner [V, k] int32: slot b of the star triangle {a, b} of the origin with cross(a, b) > 0, or -1 -- the triangles at the origin of
+    the planar Delaunay triangulation of {0} u {(X_a, Y_a)}.  Slot a pivots over the slots c on its counter-clockwise side (c replaces
+    the candidate b when it is strictly inside circle(0, a, b)), then the circle is checked against every slot; ties are not inside, so
+    the lower slot is kept.  2 k vectorised steps over all slots at once."""
+    V, k = X.shape
+    slot = np.arange(k)[None, :]
+    partner = np.full((V, k), -1, dtype=np.int32)
+    xb, yb, wb, cr_ab = (np.zeros((V, k)) for _ in range(4))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for c in range(k):
+            xc, yc, wc = X[:, c:c + 1], Y[:, c:c + 1], W[:, c:c + 1]
+            cr_ac = X * yc - Y * xc
+            cand = (W > 0) & (wc > 0) & (slot != c) & (cr_ac > STAR_CR_TOL * np.sqrt(W * wc))
+            take = cand & ((partner < 0) | (_incircle(X, Y, W, xb, yb, wb, cr_ab, xc, yc, wc) < 0))
+            partner = np.where(take, np.int32(c), partner)
+            xb, yb, wb, cr_ab = np.where(take, xc, xb), np.where(take, yc, yb), np.where(take, wc, wb), np.where(take, cr_ac, cr_ab)
+        empty = partner >= 0
+        for c in range(k):
+            xc, yc, wc = X[:, c:c + 1], Y[:, c:c + 1], W[:, c:c + 1]
+            inside = (wc > 0) & (slot != c) & (partner != c) & (_incircle(X, Y, W, xb, yb, wb, cr_ab, xc, yc, wc) < 0)
+            empty &= ~inside
+    return np.where(empty, partner, np.int32(-1))
+
+
+def cloud_laplacian_terms(pts: np.ndarray, nbr: np.ndarray, partner: np.ndarray):
+    """The per-triangle terms of the Laplacian and the mass: for every filled slot (i, a) with b = partner[i, a] the lifted triangle
+    (i, nbr[i, a], nbr[i, b]) gives, per corner, w = cot / 2 / 3 on the opposite edge (-w off the diagonal, +w on both diagonals) and
+    area / 3 / 3 to every vertex.  -> (rows, cols, vals) of L with one term per edge end, (verts, vals) of the mass, all concatenated."""
+    pts = np.asarray(pts, dtype=np.float64)
+    i, a = np.nonzero(partner >= 0)
+    v0, v1, v2 = i, nbr[i, a], nbr[i, partner[i, a]]
+    u, v = pts[v1] - pts[v0], pts[v2] - pts[v0]
+    t = v - u
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cn = np.linalg.norm(np.cross(u, v), axis=1)
+        w12 = np.einsum("ij,ij->i", u, v) / cn / 6.0
+        w02 = -np.einsum("ij,ij->i", u, t) / cn / 6.0
+        w01 = np.einsum("ij,ij->i", v, t) / cn / 6.0
+    keep = (cn > 0) & np.isfinite(w12) & np.isfinite(w02) & np.isfinite(w01) & (v1 != v0) & (v2 != v0) & (v1 != v2)
+    v0, v1, v2, cn, w12, w02, w01 = (x[keep] for x in (v0, v1, v2, cn, w12, w02, w01))
+    rows, cols, vals = [], [], []
+    for p, q, w in ((v0, v1, w01), (v0, v2, w02), (v1, v2, w12)):
+        rows += [p, q, p, q]
+        cols += [p, q, q, p]
+        vals += [w, w, -w, -w]
+    m = cn / 18.0
+    return (np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)), (np.concatenate([v0, v1, v2]), np.concatenate([m, m, m]))
+
+
+def point_cloud_laplacian_from_table(pts, nbr, frames, with_parts=False):
+    """``point_cloud_laplacian_host`` on a given neighbour table [V, k] and given frames [V, 3, 3]: (L scipy CSR fp64, mass [V] fp64).
+    ``with_parts``: also a dict with ``partner`` [V, k] and the sums of the ABSOLUTE terms of every entry, ``L_abs`` (CSR, the pattern of
+    L) and ``mass_abs`` -- what a rounding of the entry is measured against."""
+    pts = np.asarray(pts, dtype=np.float64)
+    nbr = np.asarray(nbr).astype(np.int64)
+    V = pts.shape[0]
+    if nbr.size and (nbr.min() < 0 or nbr.max() >= V):
+        raise IndexError("point-cloud Laplacian: the neighbour table holds an index outside [0, %d)" % V)
+    partner = cloud_stars(*cloud_project(pts, nbr, frames))
+    (rows, cols, vals), (mv, mw) = cloud_laplacian_terms(pts, nbr, partner)
+    # every term stands under (i, j) and under (j, i): sum the upper copies (in the order of the slots) and mirror them -- L == L^T exactly
+    up = rows <= cols
+    ukey, inv = np.unique(rows[up] * np.int64(V) + cols[up], return_inverse=True)
+    r, c = ukey // V, ukey % V
+    off = r != c
+
+    def assemble(terms):
+        s = np.bincount(inv, weights=terms, minlength=len(ukey))
+        m = sp.coo_matrix((np.concatenate([s, s[off]]), (np.concatenate([r, c[off]]), np.concatenate([c, r[off]]))), shape=(V, V)).tocsr()
+        m.sort_indices()
+        return m
+
+    L = assemble(vals[up])
+    mass = np.bincount(mv, weights=mw, minlength=V)
+    if not with_parts:
+        return L, mass
+    return L, mass, dict(partner=partner, L_abs=assemble(np.abs(vals[up])), mass_abs=mass)
+
+
+def point_cloud_laplacian_host(v64, n_neighbors=30, frames=None):
+    """Laplacian and lumped mass of a point cloud, (L scipy CSR [V, V] fp64, mass [V] fp64): the local-Delaunay construction of Sharp &
+    Crane, "A Laplacian for Nonmanifold Triangle Meshes" (2020), section 5.7 -- every point's ``n_neighbors`` nearest neighbours are
+    projected on its tangent plane, the star of the point in their planar Delaunay triangulation gives triangles, and L and the mass are
+    the cotan Laplacian and the vertex areas of all those triangles, each weighted 1/3 -- WITHOUT the intrinsic Delaunay / tufted-cover
+    re-triangulation that ``robust_laplacian.point_cloud_laplacian`` then applies.  L is symmetric, has zero row sums and is positive
+    semi-definite for any input (a sum of per-triangle Dirichlet forms); single weights can be negative on bad samplings.
+
+    ``v64`` [V, 3] positions (numpy or torch), ``frames`` [V, 3, 3] tangent frames (rows basisX, basisY, normal) or None: those of the
+    normals estimated from the same neighbourhoods, as ``geometry.cloud_operators`` does on the host.  Vectorised numpy in fp64; the HIP
+    route (``ops.cloud_laplacian``, dn_cloud_lap.hip) is the same arithmetic.  A valid ``laplacian=`` callable of ``compute_operators``."""
+    from .geometry import find_knn                 # (geometry imports this module)
+    pts = v64.detach().cpu().numpy() if isinstance(v64, torch.Tensor) else np.asarray(v64)
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    V, k = pts.shape[0], int(n_neighbors)
+    t = torch.from_numpy(pts)
+    nbr = find_knn(t, t, k, omit_diagonal=True, method="cpu_kd").indices.numpy()
+    if frames is None:
+        frames = tangent_frames(neighborhood_normal(pts[nbr] - pts[:, None, :]))
+    elif isinstance(frames, torch.Tensor):
+        frames = frames.detach().cpu().numpy()
+    return point_cloud_laplacian_from_table(pts, nbr, np.asarray(frames, dtype=np.float64).reshape(V, 3, 3))
+
+
 # ----------------------------------------------------------------------------------------- torch-facing API
 def _to_torch_sparse(mat, device, dtype):
     coo = mat.tocoo()
@@ -177,7 +305,8 @@ def _cloud_laplacian(v64, laplacian):
             raise ImportError(
                 "compute_operators on a point cloud (empty faces) needs a point-cloud Laplacian, which this package does not restate: "
                 "either pass laplacian=(L, massvec) or laplacian=<callable: fp64 positions [V,3] -> (L, M)>, "
-                "or install the robust_laplacian package (its point_cloud_laplacian is then used, as in the reference)") from err
+                "or install the robust_laplacian package (its point_cloud_laplacian is then used, as in the reference); "
+                "laplacian=\"delaunay\" builds this package's own local-Delaunay Laplacian instead") from err
         laplacian = robust_laplacian.point_cloud_laplacian
     L, M = laplacian(v64) if callable(laplacian) else laplacian
     if isinstance(M, torch.Tensor):
@@ -192,9 +321,26 @@ def _cloud_laplacian(v64, laplacian):
 
 def _compute_cloud_operators(verts, k_eig, normals, laplacian, n_neighbors_cloud=30):
     """The point-cloud branch of ``compute_operators`` (geometry.py:306-392 with is_cloud)."""
-    from .geometry import cloud_operators          # (geometry imports this module)
+    from . import geometry                         # (geometry imports this module)
     device, dtype = verts.device, verts.dtype
-    frames, gradX, gradY = cloud_operators(verts, n_neighbors_cloud, normals=normals)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)
+    if isinstance(laplacian, str):
+        if laplacian != "delaunay":
+            raise ValueError("laplacian=%r: the only named point-cloud Laplacian is \"delaunay\"" % laplacian)
+        # the frames and the neighbour table of the gradient operator serve the stars too; on a ROCm device nothing but the eigenproblem
+        # (scipy's shift-invert Lanczos, as for meshes) runs on the host
+        frames, gradX, gradY, nbr = geometry._cloud_operators_and_table(verts, n_neighbors_cloud, normals)
+        Lt, mass_t = geometry._laplacian_of_table(verts, nbr, frames)
+        L = _sparse_to_csc(Lt).astype(np.float64).tocsr()
+        mass = mass_t.detach().cpu().numpy().astype(np.float64)
+        mass = mass + EPS * mass.mean()
+        if np.isnan(L.data).any():
+            raise RuntimeError("NaN Laplace matrix")
+        if np.isnan(mass).any():
+            raise RuntimeError("NaN mass matrix")
+        evals, evecs = laplacian_eigenbasis(L, mass, k_eig)
+        return frames, t(mass), Lt, t(evals), t(evecs), gradX, gradY
+    frames, gradX, gradY = geometry.cloud_operators(verts, n_neighbors_cloud, normals=normals)
     v64 = verts.detach().cpu().numpy().astype(np.float64)
     L, mass = _cloud_laplacian(v64, laplacian)
     if np.isnan(L.data).any():
@@ -202,7 +348,6 @@ def _compute_cloud_operators(verts, k_eig, normals, laplacian, n_neighbors_cloud
     if np.isnan(mass).any():
         raise RuntimeError("NaN mass matrix")
     evals, evecs = laplacian_eigenbasis(L, mass, k_eig)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)
     return frames, t(mass), _to_torch_sparse(L, device, dtype), t(evals), t(evecs), gradX, gradY
 
 
@@ -213,7 +358,10 @@ def compute_operators(verts, faces, k_eig, normals=None, *, laplacian=None):
     Empty ``faces``: a point cloud.  Frames and gradients are those of ``geometry.cloud_operators`` (30 neighbours, as the reference);
     the Laplacian and the mass come from ``laplacian`` -- ``(L scipy sparse, massvec)`` or a callable taking the fp64 positions [V,3] and
     returning ``(L, M)`` (M a diagonal sparse matrix or a vector) -- or, without it, from ``robust_laplacian.point_cloud_laplacian`` if
-    that package is installed (ImportError otherwise)."""
+    that package is installed (ImportError otherwise).  ``laplacian="delaunay"``: this package's own local-Delaunay Laplacian
+    (``point_cloud_laplacian_host``: Sharp & Crane 2020, section 5.7, without the intrinsic / tufted re-triangulation of robust_laplacian)
+    on the frames and the neighbour table the gradient operator is built from -- on a ROCm device by the HIP kernels of
+    dn_cloud_lap.hip (``ops.cloud_laplacian``), otherwise in numpy -- with EPS x the mean mass added to the mass, as for a mesh."""
     device, dtype = verts.device, verts.dtype
     if faces.numel() == 0:
         return _compute_cloud_operators(verts, k_eig, normals, laplacian)
@@ -247,7 +395,8 @@ def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, over
     """``compute_operators`` behind the reference's on-disk npz cache (geometry.py:426-570): same key derivation, same
     file names, same array names (float32 payload, CSC triplets for L / gradX / gradY), so either implementation can
     read the other's cache.  A hit is verified against the stored verts/faces; an entry with too few eigenpairs is
-    rebuilt.  ``laplacian``: passed on to ``compute_operators`` (point clouds)."""
+    rebuilt.  ``laplacian``: passed on to ``compute_operators`` (point clouds).  The key is the reference's -- positions and faces only --
+    so a hit cannot tell which Laplacian wrote the entry: a cache directory should be filled with one ``laplacian`` choice."""
     device, dtype = verts.device, verts.dtype
     v_np, f_np = verts.detach().cpu().numpy(), faces.detach().cpu().numpy()
     if np.isnan(v_np).any():

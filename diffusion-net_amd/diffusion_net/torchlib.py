@@ -299,6 +299,20 @@ def _(src, tgt, k, largest, omit_diagonal):
     return src.new_empty(src.shape[0], k, dtype=torch.float32), src.new_empty(src.shape[0], k, dtype=torch.int64)   # ops.knn is fp32
 
 
+# ------------------------------------------------------------------------------------------------ point-cloud Laplacian (forward only)
+@_op("diffusion_net::cloud_laplacian")
+def cloud_laplacian(points: Tensor, nbr: Tensor, frames: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return ops.cloud_laplacian(points, nbr, frames)
+
+
+@cloud_laplacian.register_fake
+def _(points, nbr, frames):
+    n, k = nbr.shape
+    nnz = torch.library.get_ctx().new_dynamic_size()       # the number of entries depends on the data
+    return (points.new_empty(n, k, dtype=torch.int32), points.new_empty(n + 1, dtype=torch.int32), points.new_empty(nnz, dtype=torch.int32),
+            points.new_empty(nnz, dtype=torch.float32), points.new_empty(n, dtype=torch.float32))
+
+
 # ------------------------------------------------------------------------------------------------ functional maps (regularised spectral solve)
 @_op("diffusion_net::fmap_solve")
 def fmap_solve(A: Tensor, B: Tensor, evals_x: Tensor, evals_y: Tensor, lam: float) -> Tensor:

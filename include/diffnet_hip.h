@@ -362,6 +362,48 @@ int dn_knn_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim
 int dn_cloud_operators_f32(const float* pts, int n, const int64_t* nbr, int k, const float* normals_in, float* normals, float* frames,
                            int32_t* g_rowptr, int32_t* g_col, float* g_vx, float* g_vy, int32_t* status, void* stream);
 
+/* ---- point-cloud Laplacian and lumped mass from local Delaunay stars (dn_cloud_lap.hip): the construction of Sharp & Crane 2020, section
+ *      5.7, WITHOUT the intrinsic / tufted re-triangulation that robust_laplacian applies to the triangles (the reference takes its
+ *      point-cloud Laplacian from that package; this is not its arithmetic).  pts [n,3] fp32; nbr [n,k] int64 as dn_knn_f32 writes them
+ *      (omit_diagonal); frames [n,3,3] fp32 as dn_cloud_operators_f32 writes them (rows basisX, basisY; the normal row is not read).
+ *        star    With e_a = pts[nbr[i,a]] - pts[i], X_a = e_a.basisX, Y_a = e_a.basisY, W_a = X_a^2 + Y_a^2: the unordered pair {a, b} is a
+ *                triangle of point i iff cr = X_a Y_b - Y_a X_b satisfies |cr| > 1e-12 sqrt(W_a W_b) and no other slot c lies strictly
+ *                inside the circle through 0, a, b -- for cr > 0: W_c cr - W_b (X_a Y_c - Y_a X_c) + W_a (X_b Y_c - Y_b X_c) < 0.  A slot
+ *                whose index is i itself or whose W is 0 takes no part, as vertex or as obstacle.  In general position these are the
+ *                triangles at the origin of the planar Delaunay triangulation of {0} u {(X_a, Y_a)}.  partner [n,k] int32: partner[i,a]
+ *                is the slot b of the triangle {a, b} with cr(a, b) > 0 (each triangle once, on its clockwise slot), or -1.  Co-circular
+ *                points (in-circle exactly 0) are not inside: of two tied partners the lower slot is kept.
+ *                status: one device int32, set to the number of rows that held an index outside [0,n); such a row reads nothing through
+ *                it and has no triangle (all -1).  The caller reads the word at its next synchronisation point.
+ *        emit    For every filled slot the lifted 3-D triangle (v0, v1, v2) = (i, nbr[i,a], nbr[i,b]): with cot_c = dot / |cross| at corner c
+ *                and w_c = cot_c / 2 / 3, the edge opposite corner c gets -w_c on its two off-diagonals and +w_c on its two diagonals;
+ *                every vertex gets area / 3 / 3 of mass (the second third: in the interior a triangle shows up in the stars of all three
+ *                of its corners).  Written to the workspace (dn_cloud_laplacian_workspace_bytes(n, k) = 192 n k bytes), S = n k slots:
+ *                  int64 key_l [9 S] at byte 0, fp64 val_l [9 S] at 72 S, int64 key_m [3 S] at 144 S, fp64 val_m [3 S] at 168 S;
+ *                slot s = i k + a owns entries 9 s .. 9 s + 8 of L -- keys (row << 32 | col): the diagonals of v0, v1, v2 (each the sum of
+ *                its two edge weights), then (v0,v1) (v1,v0) (v0,v2) (v2,v0) (v1,v2) (v2,v1) -- and 3 s .. 3 s + 2 of the mass (keys v0,
+ *                v1, v2).  An empty slot (partner -1 or out of range, an index out of range, a lifted triangle without area) writes the
+ *                key INT64_MAX, which sorts last, and the value 0.
+ *        sum     dn_segment_sum_f64_f32 on keys [m] sorted ascending by a STABLE sort, perm [m] int64 (position of each sorted key
+ *                in the unsorted arrays), vals [m] fp64 (unsorted): every run of equal keys other than INT64_MAX is added in sorted order
+ *                in fp64 and rounded to fp32 once.  rowptr != NULL: keys are (row << 32 | col) with row, col in [0, n_rows); rank [m] int64
+ *                is the inclusive count of run heads (keys[p] != keys[p-1]) up to p; the r-th run goes to col[r], out[r] (both [m]),
+ *                rowptr [n_rows + 1] is filled and *count (device int32) set to the number of runs: CSR with ascending columns.
+ *                rowptr == NULL (col, rank, count unused): keys index out [n_rows], which is zeroed first.
+ *      L = sum over all stars is symmetric with zero row sums and positive semi-definite for ANY input (a sum of per-triangle Dirichlet
+ *      forms); without the intrinsic re-triangulation single weights can be negative on bad samplings.  Everything from the coordinate
+ *      differences on is fp64.  No floating-point atomics: the result is bit-identical from run to run, and entries (i,j) and (j,i)
+ *      are sums of the same terms in the same order -- the same bits.
+ *      Each returns 0 on success (n == 0, or m == 0 and n_rows == 0: nothing is launched) and non-zero WITHOUT launching for k < 1,
+ *      k > DN_KNN_MAX_K, n < 0, 9 n k > INT32_MAX (the query returns 0 bytes for these), m < 0, n_rows < 0, a workspace smaller than
+ *      the query says, or a NULL pointer that the call would use. */
+size_t dn_cloud_laplacian_workspace_bytes(int n, int k);
+int dn_cloud_star_f32(const float* pts, int n, const int64_t* nbr, int k, const float* frames, int32_t* partner, int32_t* status, void* stream);
+int dn_cloud_laplacian_emit_f32(const float* pts, int n, const int64_t* nbr, int k, const int32_t* partner, void* ws, size_t ws_bytes,
+                                void* stream);
+int dn_segment_sum_f64_f32(const int64_t* keys, const int64_t* perm, const double* vals, int m, const int64_t* rank, int n_rows,
+                           int32_t* rowptr, int32_t* col, float* out, int32_t* count, void* stream);
+
 /* ---- functional maps (experiments/functional_correspondence/fmaps_model.py:11-40): the regularised spectral solve and its backward
  *      (dn_fmap.hip).  A, B [P, K, F] fp32 row-major: the spectral coefficients of the features of shapes x and y of P pairs;
  *      evals_x, evals_y [P, K] fp32; lam: the regularisation weight.  With G = A A^T, H = B A^T and
