@@ -8,3 +8,4 @@ from . import utils, geometry, layers, synthetic, batch, ops, graphs, autograph,
 from .batch import MeshBatch, GatherPattern  # noqa: F401
 from .layers import DiffusionNet  # noqa: F401
 from .geometry import find_knn, geodesic_distances, geodesic_label_errors, get_all_pairs_geodesic_distance, point_cloud_laplacian  # noqa: F401
+from .geometry import laplacian_eigenbasis  # noqa: F401

@@ -18,6 +18,7 @@ import torch
 from . import ops
 from .batch import MeshBatch
 from .precompute import compute_operators, get_all_operators, get_operators, neighborhood_normal, normalize_positions  # noqa: F401
+from .precompute import compute_operators_with  # noqa: F401
 from . import precompute as _pre
 
 
@@ -293,6 +294,107 @@ def point_cloud_laplacian(verts, n_neighbors=30, frames=None):
         return _laplacian_of_table(verts, nbr, frames)
     L, mass = _pre.point_cloud_laplacian_host(verts.detach().cpu().numpy(), n_neighbors, frames)
     return _pre._to_torch_sparse(L, verts.device, verts.dtype), torch.from_numpy(mass).to(device=verts.device, dtype=verts.dtype)
+
+
+# ----------------------------------------------------------------------------------------------
+# Laplacian eigenbasis: Chebyshev-filtered subspace iteration, the products with S on the device (dn_eigen.hip)
+# ----------------------------------------------------------------------------------------------
+class _TorchBlocks:
+    """The block operations of ``precompute.subspace_iterate`` on fp64 torch blocks [V, nb]: every product with S is ``ops.cheb_step``, the
+    tall dense products are torch calls on the same device; only nb x nb matrices and k residual norms cross to the host."""
+    route = "kernel"
+
+    def __init__(self, S, dev):
+        import numpy as np
+        self.dev = dev
+        self.rowptr = torch.from_numpy(S.indptr.astype(np.int32)).to(dev)
+        self.col = torch.from_numpy(S.indices.astype(np.int32)).to(dev)
+        self.val = torch.from_numpy(S.data.astype(np.float64)).to(dev)
+
+    def from_host(self, a):
+        import numpy as np
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
+
+    def to_host(self, a):
+        return a.cpu().numpy()
+
+    def step(self, Y, Z, alpha, beta, gamma, out=None):
+        return ops.cheb_step(self.rowptr, self.col, self.val, Y, Z, alpha, beta, gamma, out=out)
+
+    def tmm(self, A, B):
+        return A.t() @ B
+
+    def mm(self, A, B):
+        return A @ B
+
+    def solve_upper_right(self, X, R):          # X R^-1
+        return torch.linalg.solve_triangular(R, X, upper=True, left=False).contiguous()
+
+    def residuals(self, SX, X, w, k):
+        return torch.linalg.vector_norm(SX[:, :k] - X[:, :k] * w[:k], dim=0)
+
+    def finish(self, X, d, k):
+        evecs = X[:, :k] * d[:, None]
+        mag = evecs.abs()
+        first = (mag == mag.max(dim=0, keepdim=True).values).to(torch.int8).argmax(dim=0)      # the first index of the largest magnitude
+        sign = 1.0 - 2.0 * (evecs.gather(0, first[None, :]) < 0).to(evecs.dtype)
+        return evecs * sign
+
+
+def _eigen_on_device():
+    return torch.cuda.is_available() or ops._hip._allow_host_tensors
+
+
+def _scipy_of(L):
+    import scipy.sparse
+    if isinstance(L, torch.Tensor):
+        if L.layout != torch.sparse_coo:
+            L = L.to_sparse() if L.layout == torch.strided else L.to_sparse_coo()
+        return _pre._sparse_to_csc(L).tocsr()
+    return scipy.sparse.csr_matrix(L)
+
+
+def laplacian_eigenbasis(L, massvec, k_eig, *, rtol=1e-9, seed=0, max_iter=100, dtype=None, return_info=False):
+    """The ``k_eig`` smallest pairs of (L + EPS I) phi = lambda M phi, M = diag(massvec) -- the pencil of ``compute_operators`` -- by
+    Chebyshev-filtered subspace iteration (``precompute.subspace_iterate``), without a sparse factorisation: (evals [k] ascending, clipped at
+    0; evecs [V, k] M-orthonormal, each column signed so that its entry of largest magnitude, the first on ties, is positive) as torch
+    tensors on the device of ``massvec`` in ``dtype`` (default: ``massvec``'s).  All arithmetic is fp64.  ``L``: a torch sparse tensor or a
+    scipy matrix [V, V], symmetric positive semi-definite; ``massvec`` [V] positive (torch, or array-like: the host).
+
+    With a ROCm device every product with S = D (L + EPS I) D, D = diag(massvec^-1/2), is ``ops.cheb_step`` (dn_eigen.hip) and the tall
+    dense products are fp64 torch calls on that device; the nb x nb ``eigh`` and Cholesky factorisations, nb = k + max(16, ceil(k / 4)),
+    run on the host (a few small transfers and synchronisations per outer iteration, of which there are 3 .. 9).  Without a device: the
+    same driver on numpy / scipy (``precompute.laplacian_eigenbasis_subspace``).  2 nb > V: ``scipy.linalg.eigh`` of the dense pencil on the
+    host, in either case.  The starting block is drawn on the host from ``numpy.random.default_rng(seed)``: both routes start alike.
+    ``return_info``: also a dict -- ``route`` ("kernel", "numpy", "dense" or "empty"), ``nb``, ``ub`` (the Gershgorin bound of S),
+    ``iterations``, ``products`` (with S), ``degrees`` (of the filters) and ``residual`` (max_i ||S x_i - w_i x_i||_2 at the end).
+    ``RuntimeError`` if a Cholesky factorisation fails or ``max_iter`` iterations do not reach ``rtol``: there is no fallback."""
+    import numpy as np
+    if not isinstance(massvec, torch.Tensor):
+        massvec = torch.as_tensor(np.asarray(massvec))
+    out_dev = massvec.device
+    out_dtype = dtype if dtype is not None else (massvec.dtype if massvec.dtype.is_floating_point else torch.float64)
+    m = massvec.detach().cpu().numpy().astype(np.float64).reshape(-1)
+    Ls = _scipy_of(L)
+    V, k = Ls.shape[0], int(k_eig)
+    if Ls.shape != (V, V) or m.shape != (V,):
+        raise ValueError("laplacian_eigenbasis: L %s and massvec %s do not fit" % (Ls.shape, m.shape))
+    if k < 0:
+        raise ValueError("laplacian_eigenbasis: k_eig = %d" % k)
+    if k == 0 or 2 * _pre.subspace_block_width(k) > V or not _eigen_on_device():
+        evals, evecs, info = _pre.laplacian_eigenbasis_subspace(Ls, m, k, rtol=rtol, seed=seed, max_iter=max_iter, return_info=True)
+        evals, evecs = torch.from_numpy(np.ascontiguousarray(evals)), torch.from_numpy(np.ascontiguousarray(evecs))
+    else:
+        # (host buffers only while the test suite has bound the emulator build of the library, which cannot read device memory)
+        if ops._hip._allow_host_tensors:
+            dev = torch.device("cpu")
+        else:
+            dev = out_dev if out_dev.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+        S, d, ub = _pre.scaled_operator(Ls, m)
+        evals, evecs, info = _pre.subspace_iterate(_TorchBlocks(S, dev), V, d, ub, k, rtol, seed, max_iter)
+        evals = torch.from_numpy(np.ascontiguousarray(evals))
+    evals, evecs = evals.to(device=out_dev, dtype=out_dtype), evecs.to(device=out_dev, dtype=out_dtype)
+    return (evals, evecs, info) if return_info else (evals, evecs)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
+import weakref
 from typing import List, NamedTuple, Optional
 
 import torch
@@ -459,6 +460,91 @@ def minplus_distances(rowptr, col, w, sources, *, sweeps_per_check=8, max_block_
         src = sources[s0:s0 + per_block]
         out[s0:s0 + src.numel()] = _minplus_block(rowptr, col, w, src, n_nodes, sweeps_per_check).t()
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Laplacian eigenbasis: one Chebyshev recurrence step on a block of vectors (include/diffnet_hip.h: dn_cheb_step_f64)
+# ----------------------------------------------------------------------------------------------
+_cheb_checked = None      # (weakref rowptr, weakref col, their versions): the CSR pattern the last call validated
+
+
+def _cheb_check_pattern(rowptr, col, n_rows):
+    """Row pointer and column range of a CSR pattern, read back from the device ONCE per pattern: the calls of a solve share one."""
+    global _cheb_checked
+    seen = _cheb_checked
+    if seen is not None and seen[0]() is rowptr and seen[1]() is col and seen[2] == (rowptr._version, col._version, n_rows):
+        return
+    nnz = col.numel()
+    rp = rowptr.to(torch.int64)
+    if int(rp[0]) != 0 or int(rp[-1]) != nnz or (n_rows and bool((rp[1:] < rp[:-1]).any())):
+        raise ValueError("cheb_step: rowptr is not a non-decreasing row pointer of %d entries" % nnz)
+    if nnz and (int(col.min()) < 0 or int(col.max()) >= n_rows):
+        raise ValueError("cheb_step: a column index is outside [0, %d)" % n_rows)
+    _cheb_checked = (weakref.ref(rowptr), weakref.ref(col), (rowptr._version, col._version, n_rows))
+
+
+def _cheb_block(name, t, n_rows, like):
+    if (t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != n_rows or (t.shape[1] > 1 and t.stride(1) != 1)
+            or (n_rows > 1 and t.stride(0) < t.shape[1])):
+        raise TypeError("cheb_step: %s must be an fp64 block [%d, nb] with unit column stride (got %s %s, strides %s)"
+                        % (name, n_rows, t.dtype, tuple(t.shape), t.stride()))
+    if like is not None and (t.shape != like.shape or _cheb_ld(t) != _cheb_ld(like) or t.device != like.device):
+        raise ValueError("cheb_step: %s %s (leading dimension %d, %s) does not match Y %s (%d, %s)"
+                         % (name, tuple(t.shape), _cheb_ld(t), t.device, tuple(like.shape), _cheb_ld(like), like.device))
+
+
+def _cheb_ld(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+@_on_device
+def _cheb_launch(rowptr, col, val, Y, Z, out, alpha, beta, gamma):
+    _hip.check(_hip.lib().dn_cheb_step_f64(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), Y.shape[0], Y.data_ptr(), _hip.ptr(Z),
+                                           out.data_ptr(), Y.shape[1], _cheb_ld(Y), alpha, beta, gamma, _hip.stream_of(Y)), "dn_cheb_step_f64")
+    return out
+
+
+def cheb_step(rowptr, col, val, Y, Z, alpha, beta, gamma, out=None):
+    """``out = alpha * S @ Y + beta * Y + gamma * Z`` for S in CSR (dn_eigen.hip), forward only: one step of the Chebyshev three-term
+    recurrence on a block of vectors.  ``rowptr`` [n + 1], ``col`` [nnz] int32, ``val`` [nnz] fp64; ``Y``, ``Z``, ``out`` fp64 blocks
+    [n, nb] with unit column stride and ONE row stride (the leading dimension, >= nb: column slices of wider blocks are taken as they
+    are, what lies beside them is neither read nor written).  ``Z`` may be None when ``gamma == 0``; a term whose scalar is 0 is not formed.
+    ``out`` None: a new contiguous block; ``out`` may be ``Z``, never ``Y``.  One fma per entry in CSR order, no atomics: two calls give the
+    same bits.  No synchronisation, except that the pattern (rowptr, col) is validated on its first use (``ValueError``)."""
+    for t in (rowptr, col, val, Y):
+        _hip.require_device(t)
+    if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or val.dtype != torch.float64:
+        raise TypeError("cheb_step takes int32 rowptr and col and fp64 values (got %s, %s, %s)" % (rowptr.dtype, col.dtype, val.dtype))
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1 or val.dim() != 1 or col.numel() != val.numel():
+        raise ValueError("cheb_step takes CSR arrays rowptr [n + 1], col [nnz], val [nnz]")
+    if not (rowptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()):
+        raise ValueError("cheb_step takes contiguous CSR arrays")
+    n_rows = rowptr.numel() - 1
+    alpha, beta, gamma = float(alpha), float(beta), float(gamma)
+    _cheb_block("Y", Y, n_rows, None)
+    if not (rowptr.device == col.device == val.device == Y.device):
+        raise RuntimeError("cheb_step: the operands are on %s, %s, %s and %s" % (rowptr.device, col.device, val.device, Y.device))
+    if Z is None and gamma != 0.0:
+        raise ValueError("cheb_step: gamma = %g needs Z" % gamma)
+    if Z is not None:
+        _hip.require_device(Z)
+        _cheb_block("Z", Z, n_rows, Y)
+    if out is None:
+        if _cheb_ld(Y) == Y.shape[1]:
+            out = torch.empty_like(Y)
+        else:                                    # Y is a column slice: a block of its leading dimension, sliced alike
+            out = torch.empty(n_rows, _cheb_ld(Y), dtype=torch.float64, device=Y.device)[:, :Y.shape[1]]
+    else:
+        _hip.require_device(out)
+        _cheb_block("out", out, n_rows, Y)
+        if out.data_ptr() == Y.data_ptr() and out.numel():
+            raise ValueError("cheb_step: out must not be Y (other rows of Y are read while out is written)")
+    if n_rows == 0 or Y.shape[1] == 0:
+        return out
+    if col.numel() == 0:
+        raise ValueError("cheb_step: S has no entries")
+    _cheb_check_pattern(rowptr, col, n_rows)
+    return _cheb_launch(rowptr, col, val, Y, Z, out, alpha, beta, gamma)
 
 
 # ----------------------------------------------------------------------------------------------

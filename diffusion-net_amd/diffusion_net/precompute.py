@@ -162,6 +162,195 @@ def laplacian_eigenbasis(L: sp.spmatrix, massvec: np.ndarray, k_eig: int):
             A = A + sp.identity(L.shape[0]) * (EPS * 10 ** fails)
 
 
+# ----------------------------------------------------------------------------------------- eigenbasis by filtered subspace iteration
+# The same pencil, (L + eps I) phi = lambda M phi, without a sparse factorisation: with D = diag(massvec^-1/2) and S = D (L + eps I) D
+# (symmetric, CSR, fp64) the k smallest pairs of S x = lambda x give phi = D x.  A block X of nb = k + max(16, ceil(k / 4)) orthonormal
+# columns is Rayleigh-Ritz'ed (H = X^T S X, (w, Q) = eigh(H), X <- X Q) and, until the first k residuals ||S x_i - w_i x_i|| fall below
+# rtol w_k, filtered by the Chebyshev polynomial T_m((S - c) / e) of the interval [a, ub] = [w_nb, Gershgorin bound] -- which damps what the
+# block does not want and grows what lies below a -- and re-orthonormalised by Cholesky-QR applied twice.  The degree m is the smallest
+# that separates the block's own ends by at most SUBSPACE_AMP = 1e6: that bounds the condition number of the filtered block (measured:
+# at most 2.8e6), and Cholesky-QR is valid below about 1e8.  One driver serves the numpy route (scipy products, here) and the device route
+# (geometry.laplacian_eigenbasis: the products are dn_eigen.hip, the tall dense products torch); the nb x nb eigh and Cholesky run on the
+# host in both.
+SUBSPACE_AMP = 1e6
+SUBSPACE_MAX_DEGREE = 64
+
+
+def subspace_block_width(k_eig: int) -> int:
+    return int(k_eig) + max(16, -(-int(k_eig) // 4))
+
+
+def scaled_operator(L, massvec: np.ndarray):
+    """S = D (L + eps I) D as scipy CSR fp64 with sorted indices, d = massvec^-1/2, ub = max_i sum_j |S_ij| (Gershgorin)."""
+    V = L.shape[0]
+    m = np.asarray(massvec, dtype=np.float64).reshape(-1)
+    if m.shape[0] != V or not (m > 0).all():
+        raise ValueError("laplacian eigenbasis: the mass must be %d positive numbers" % V)
+    d = 1.0 / np.sqrt(m)
+    Dm = sp.diags(d)
+    S = (Dm @ (sp.csr_matrix(L).astype(np.float64) + sp.identity(V, format="csr") * EPS) @ Dm).tocsr()
+    S.sum_duplicates()
+    S.sort_indices()
+    ub = float(abs(S).sum(axis=1).max()) if V else 0.0
+    if not np.isfinite(ub):
+        raise ValueError("laplacian eigenbasis: L and the mass must be finite")
+    return S, d, ub
+
+
+class _NumpyBlocks:
+    """The block operations of ``subspace_iterate`` in numpy / scipy (the device route's: geometry._TorchBlocks)."""
+    route = "numpy"
+
+    def __init__(self, S):
+        self.S = S
+
+    def from_host(self, a):
+        return np.array(a, dtype=np.float64)
+
+    def to_host(self, a):
+        return np.asarray(a)
+
+    def step(self, Y, Z, alpha, beta, gamma, out=None):
+        r = alpha * (self.S @ Y)
+        if beta != 0.0:
+            r += beta * Y
+        if gamma != 0.0:
+            r += gamma * Z
+        return r
+
+    def tmm(self, A, B):
+        return A.T @ B
+
+    def mm(self, A, B):
+        return A @ B
+
+    def solve_upper_right(self, X, R):          # X R^-1
+        import scipy.linalg as la
+        return la.solve_triangular(R, X.T, trans="T", lower=False).T
+
+    def residuals(self, SX, X, w, k):
+        return np.linalg.norm(SX[:, :k] - X[:, :k] * w[:k], axis=0)
+
+    def finish(self, X, d, k):
+        evecs = X[:, :k] * d[:, None]
+        top = np.abs(evecs).argmax(axis=0)      # the first index of the largest magnitude
+        sign = np.where(evecs[top, np.arange(k)] < 0, -1.0, 1.0)
+        return evecs * sign
+
+
+def _cholesky_upper(G, what):
+    import scipy.linalg as la
+    try:
+        R = la.cholesky((G + G.T) * 0.5, lower=False)
+    except la.LinAlgError as err:
+        raise RuntimeError("laplacian eigenbasis (subspace): Cholesky-QR failed %s: %s" % (what, err)) from err
+    if not np.isfinite(R).all():
+        raise RuntimeError("laplacian eigenbasis (subspace): Cholesky-QR failed %s: non-finite factor" % what)
+    return R
+
+
+def _cholqr2(be, X, what):
+    for _ in range(2):
+        R = _cholesky_upper(be.to_host(be.tmm(X, X)), what)
+        X = be.solve_upper_right(X, be.from_host(R))
+    return X
+
+
+def subspace_iterate(be, V, d, ub, k_eig, rtol=1e-9, seed=0, max_iter=100):
+    """The driver: ``be`` supplies the block operations (products with S, tall dense products), this function the algorithm and the small
+    factorisations (scipy, on the host).  -> (evals [k] numpy, evecs [V, k] in ``be``'s array type, info dict).  ``RuntimeError`` with the
+    iteration and the residual when Cholesky fails or ``max_iter`` Rayleigh-Ritz rounds do not reach ``rtol``: there is no fallback."""
+    import math
+    import scipy.linalg as la
+    k, nb = int(k_eig), subspace_block_width(k_eig)
+    info = dict(route=be.route, nb=nb, ub=ub, iterations=0, products=0, degrees=[], residual=float("inf"), rtol=float(rtol))
+    X0 = np.random.default_rng(seed).standard_normal((V, nb))          # made on the host: every route starts from the same block
+    X = _cholqr2(be, be.from_host(X0), "on the starting block")
+    res = float("inf")
+    for it in range(int(max_iter)):
+        SX = be.step(X, None, 1.0, 0.0, 0.0)
+        info["products"] += 1
+        H = be.to_host(be.tmm(X, SX))
+        w, Q = la.eigh((H + H.T) * 0.5)
+        Qb = be.from_host(Q)
+        X, SX = be.mm(X, Qb), be.mm(SX, Qb)
+        res = float(np.max(be.to_host(be.residuals(SX, X, be.from_host(w), k))))
+        info["iterations"], info["residual"] = it + 1, res
+        if not np.isfinite(res):
+            raise RuntimeError("laplacian eigenbasis (subspace): non-finite residual in iteration %d" % (it + 1))
+        if res <= rtol * w[k - 1]:
+            evecs = be.finish(X, be.from_host(d), k)
+            return np.clip(w[:k], 0.0, np.inf), evecs, info
+        if it + 1 == int(max_iter):
+            break
+        a = float(w[-1])
+        if not a < ub:
+            raise RuntimeError("laplacian eigenbasis (subspace): the block's largest Ritz value %g is not below the bound %g of the spectrum "
+                               "(iteration %d, residual %g)" % (a, ub, it + 1, res))
+        c, e = (ub + a) / 2.0, (ub - a) / 2.0
+        deg = int(min(SUBSPACE_MAX_DEGREE, max(2, math.ceil(math.acosh(SUBSPACE_AMP) / math.acosh((ub + a) / (ub - a))))))
+        info["degrees"].append(deg)
+        prev, cur = X, be.step(X, None, 1.0 / e, -c / e, 0.0)            # T_0 X, T_1 X
+        for _ in range(2, deg + 1):                                      # T_(j+1) = 2 ((S - c) / e) T_j - T_(j-1), written over T_(j-1)
+            prev, cur = cur, be.step(cur, prev, 2.0 / e, -2.0 * c / e, -1.0, out=prev)
+        info["products"] += deg
+        X = _cholqr2(be, cur, "in iteration %d (residual %g)" % (it + 1, res))
+    raise RuntimeError("laplacian eigenbasis (subspace): %d iterations did not reach rtol = %g (residual %g, needs %g)"
+                       % (int(max_iter), rtol, res, rtol * w[k - 1]))
+
+
+def _dense_eigenbasis(L, massvec, k):
+    """Tiny meshes (2 nb > V): the dense pencil on the host."""
+    import scipy.linalg as la
+    V = L.shape[0]
+    if k > V:
+        raise ValueError("laplacian eigenbasis: %d eigenpairs asked of a %d x %d pencil" % (k, V, V))
+    A = (sp.csr_matrix(L).astype(np.float64) + sp.identity(V, format="csr") * EPS).toarray()
+    w, U = la.eigh((A + A.T) * 0.5, np.diag(np.asarray(massvec, dtype=np.float64)), subset_by_index=[0, k - 1])
+    top = np.abs(U).argmax(axis=0)
+    U = U * np.where(U[top, np.arange(k)] < 0, -1.0, 1.0)
+    return np.clip(w, 0.0, np.inf), U
+
+
+def laplacian_eigenbasis_subspace(L, massvec, k_eig, *, rtol=1e-9, seed=0, max_iter=100, return_info=False):
+    """``laplacian_eigenbasis`` by Chebyshev-filtered subspace iteration in numpy / scipy, fp64: (evals [k] ascending and clipped at 0,
+    evecs [V, k] M-orthonormal, each column signed so that its entry of largest magnitude -- the first on ties -- is positive).  The same
+    pencil (L + EPS I) phi = lambda M phi and the same driver as ``geometry.laplacian_eigenbasis``, which runs the products on the device.
+    2 nb > V (nb = k + max(16, ceil(k / 4))): ``scipy.linalg.eigh`` of the dense pencil instead.  ``return_info``: also a dict with the
+    route, nb, ub, iterations, products with S, filter degrees and the final residual.  ``RuntimeError`` if Cholesky-QR fails or
+    ``max_iter`` iterations do not reach ``rtol``."""
+    V, k = L.shape[0], int(k_eig)
+    m = np.asarray(massvec, dtype=np.float64).reshape(-1)
+    if k == 0:
+        out = (np.zeros((0,)), np.zeros((V, 0)))
+        info = dict(route="empty", nb=0, ub=0.0, iterations=0, products=0, degrees=[], residual=0.0, rtol=float(rtol))
+    elif 2 * subspace_block_width(k) > V:
+        out = _dense_eigenbasis(L, m, k)
+        info = dict(route="dense", nb=subspace_block_width(k), ub=0.0, iterations=0, products=0, degrees=[], residual=0.0, rtol=float(rtol))
+    else:
+        S, d, ub = scaled_operator(L, m)
+        evals, evecs, info = subspace_iterate(_NumpyBlocks(S), V, d, ub, k, rtol, seed, max_iter)
+        out = (evals, evecs)
+    return (*out, info) if return_info else out
+
+
+EIGENSOLVERS = (None, "subspace")
+
+
+def _eigenbasis(L, mass, k_eig, eigensolver, device):
+    """(evals, evecs) numpy fp64 of ``compute_operators``: shift-invert ``eigsh`` (None) or ``geometry.laplacian_eigenbasis``."""
+    if eigensolver is None:
+        return laplacian_eigenbasis(L, mass, k_eig)
+    from . import geometry                         # (geometry imports this module)
+    evals, evecs = geometry.laplacian_eigenbasis(L, torch.from_numpy(np.ascontiguousarray(mass, dtype=np.float64)).to(device), k_eig)
+    return evals.detach().cpu().numpy(), evecs.detach().cpu().numpy()
+
+
+def _check_eigensolver(eigensolver):
+    if eigensolver not in EIGENSOLVERS:
+        raise ValueError("eigensolver=%r: None (shift-invert eigsh) or \"subspace\"" % (eigensolver,))
+
+
 # ----------------------------------------------------------------------------------------- point-cloud Laplacian (local Delaunay stars)
 STAR_CR_TOL = 1e-12   # |cross(a, b)| <= STAR_CR_TOL sqrt(W_a W_b): a, b and the centre are collinear (dn_cloud_lap.hip: LP_CR_TOL)
 
@@ -319,7 +508,7 @@ def _cloud_laplacian(v64, laplacian):
     return L, mass
 
 
-def _compute_cloud_operators(verts, k_eig, normals, laplacian, n_neighbors_cloud=30):
+def _compute_cloud_operators(verts, k_eig, normals, laplacian, n_neighbors_cloud=30, eigensolver=None):
     """The point-cloud branch of ``compute_operators`` (geometry.py:306-392 with is_cloud)."""
     from . import geometry                         # (geometry imports this module)
     device, dtype = verts.device, verts.dtype
@@ -338,7 +527,7 @@ def _compute_cloud_operators(verts, k_eig, normals, laplacian, n_neighbors_cloud
             raise RuntimeError("NaN Laplace matrix")
         if np.isnan(mass).any():
             raise RuntimeError("NaN mass matrix")
-        evals, evecs = laplacian_eigenbasis(L, mass, k_eig)
+        evals, evecs = _eigenbasis(L, mass, k_eig, eigensolver, device)
         return frames, t(mass), Lt, t(evals), t(evecs), gradX, gradY
     frames, gradX, gradY = geometry.cloud_operators(verts, n_neighbors_cloud, normals=normals)
     v64 = verts.detach().cpu().numpy().astype(np.float64)
@@ -347,7 +536,7 @@ def _compute_cloud_operators(verts, k_eig, normals, laplacian, n_neighbors_cloud
         raise RuntimeError("NaN Laplace matrix")
     if np.isnan(mass).any():
         raise RuntimeError("NaN mass matrix")
-    evals, evecs = laplacian_eigenbasis(L, mass, k_eig)
+    evals, evecs = _eigenbasis(L, mass, k_eig, eigensolver, device)
     return frames, t(mass), _to_torch_sparse(L, device, dtype), t(evals), t(evecs), gradX, gradY
 
 
@@ -361,10 +550,23 @@ def compute_operators(verts, faces, k_eig, normals=None, *, laplacian=None):
     that package is installed (ImportError otherwise).  ``laplacian="delaunay"``: this package's own local-Delaunay Laplacian
     (``point_cloud_laplacian_host``: Sharp & Crane 2020, section 5.7, without the intrinsic / tufted re-triangulation of robust_laplacian)
     on the frames and the neighbour table the gradient operator is built from -- on a ROCm device by the HIP kernels of
-    dn_cloud_lap.hip (``ops.cloud_laplacian``), otherwise in numpy -- with EPS x the mean mass added to the mass, as for a mesh."""
+    dn_cloud_lap.hip (``ops.cloud_laplacian``), otherwise in numpy -- with EPS x the mean mass added to the mass, as for a mesh.
+
+    The eigenbasis is shift-invert ``eigsh`` on the host, as the reference's; ``compute_operators_with`` takes the choice of another solver
+    (this function keeps the parameter list it has had)."""
+    return compute_operators_with(verts, faces, k_eig, normals, laplacian=laplacian, eigensolver=None)
+
+
+def compute_operators_with(verts, faces, k_eig, normals=None, *, laplacian=None, eigensolver=None):
+    """``compute_operators`` with the choice of the eigensolver (``get_operators`` and ``get_all_operators`` take the same keyword and pass it
+    here).  ``eigensolver``: None -- shift-invert ``eigsh`` on the host, as the reference -- or ``"subspace"``:
+    ``geometry.laplacian_eigenbasis``, Chebyshev-filtered subspace iteration whose products run on the device (dn_eigen.hip) where there is
+    one, for meshes and for both point-cloud branches alike.  The pairs solve the same pencil to ``rtol = 1e-9``; the eigenvectors differ by
+    sign (and by a rotation inside a repeated eigenvalue), the six other outputs are identical.  Anything else: ``ValueError``."""
+    _check_eigensolver(eigensolver)
     device, dtype = verts.device, verts.dtype
     if faces.numel() == 0:
-        return _compute_cloud_operators(verts, k_eig, normals, laplacian)
+        return _compute_cloud_operators(verts, k_eig, normals, laplacian, eigensolver=eigensolver)
     if laplacian is not None:
         raise ValueError("laplacian= is for point clouds (empty faces); a triangle mesh gets its cotan Laplacian")
     v = verts.detach().cpu().numpy().astype(np.float64)
@@ -378,7 +580,7 @@ def compute_operators(verts, faces, k_eig, normals=None, *, laplacian=None):
         raise RuntimeError("NaN Laplace matrix")
     if np.isnan(mass).any():
         raise RuntimeError("NaN mass matrix")
-    evals, evecs = laplacian_eigenbasis(L, mass, k_eig)
+    evals, evecs = _eigenbasis(L, mass, k_eig, eigensolver, device)
     Lc = L.tocoo()
     grad = gradient_operator(v, frames, np.stack([Lc.row, Lc.col]))
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)
@@ -391,12 +593,15 @@ def _sparse_to_csc(t):
     return sp.coo_matrix((val, (idx[0], idx[1])), shape=tuple(t.shape)).tocsc()
 
 
-def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, overwrite_cache=False, *, laplacian=None):
+def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, overwrite_cache=False, *, laplacian=None, eigensolver=None):
     """``compute_operators`` behind the reference's on-disk npz cache (geometry.py:426-570): same key derivation, same
     file names, same array names (float32 payload, CSC triplets for L / gradX / gradY), so either implementation can
     read the other's cache.  A hit is verified against the stored verts/faces; an entry with too few eigenpairs is
     rebuilt.  ``laplacian``: passed on to ``compute_operators`` (point clouds).  The key is the reference's -- positions and faces only --
-    so a hit cannot tell which Laplacian wrote the entry: a cache directory should be filled with one ``laplacian`` choice."""
+    so a hit cannot tell which Laplacian wrote the entry: a cache directory should be filled with one ``laplacian`` choice.
+    ``eigensolver``: None or "subspace" (``compute_operators_with``); it is not part of the key either, so the same holds: a cache directory
+    should be filled with one ``eigensolver`` choice."""
+    _check_eigensolver(eigensolver)
     device, dtype = verts.device, verts.dtype
     v_np, f_np = verts.detach().cpu().numpy(), faces.detach().cpu().numpy()
     if np.isnan(v_np).any():
@@ -425,7 +630,10 @@ def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, over
                         _to_torch_sparse(rd("gradY"), device, dtype))
             except Exception:              # unreadable entry: rebuild in place  # noqa: BLE001
                 break
-    out = compute_operators(verts, faces, k_eig, normals=normals, laplacian=laplacian)
+    if eigensolver is None:
+        out = compute_operators(verts, faces, k_eig, normals=normals, laplacian=laplacian)
+    else:
+        out = compute_operators_with(verts, faces, k_eig, normals=normals, laplacian=laplacian, eigensolver=eigensolver)
     if path is not None:
         frames, mass, L, evals, evecs, gX, gY = out
         f32 = lambda a: a.detach().cpu().numpy().astype(np.float32)
@@ -438,12 +646,14 @@ def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, over
     return out
 
 
-def get_all_operators(verts_list, faces_list, k_eig, op_cache_dir=None, normals=None, *, laplacian=None):
-    """Lists in, seven lists out (geometry.py:395-424).  ``laplacian``: None, one value for every entry, or a list with one per entry."""
+def get_all_operators(verts_list, faces_list, k_eig, op_cache_dir=None, normals=None, *, laplacian=None, eigensolver=None):
+    """Lists in, seven lists out (geometry.py:395-424).  ``laplacian``: None, one value for every entry, or a list with one per entry.
+    ``eigensolver``: one value for every entry (``compute_operators_with``)."""
+    _check_eigensolver(eigensolver)
     cols = [[] for _ in range(7)]
     for i, (v, f) in enumerate(zip(verts_list, faces_list)):
         lap = laplacian[i] if isinstance(laplacian, list) else laplacian
-        res = get_operators(v, f, k_eig, op_cache_dir, normals=None if normals is None else normals[i], laplacian=lap)
+        res = get_operators(v, f, k_eig, op_cache_dir, normals=None if normals is None else normals[i], laplacian=lap, eigensolver=eigensolver)
         for c, r in zip(cols, res):
             c.append(r)
     return tuple(cols)

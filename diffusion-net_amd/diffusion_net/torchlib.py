@@ -345,3 +345,15 @@ def _fmap_setup(ctx, inputs, output):
 
 fmap_solve.register_autograd(lambda ctx, grad: (*fmap_solve_bwd(grad.contiguous(), *ctx.saved_tensors, ctx.lam), None, None, None),
                              setup_context=_fmap_setup)
+
+
+# ------------------------------------------------------------------------------------------------ Laplacian eigenbasis (forward only)
+@_op("diffusion_net::cheb_step")
+def cheb_step(rowptr: Tensor, col: Tensor, val: Tensor, Y: Tensor, Z: Optional[Tensor], alpha: float, beta: float, gamma: float) -> Tensor:
+    """``alpha * S @ Y + beta * Y + gamma * Z`` into a new block (``ops.cheb_step`` without ``out``: a custom operator mutates nothing)."""
+    return ops.cheb_step(rowptr, col, val, Y, Z, alpha, beta, gamma)
+
+
+@cheb_step.register_fake
+def _(rowptr, col, val, Y, Z, alpha, beta, gamma):
+    return Y.new_empty(Y.shape, dtype=torch.float64)

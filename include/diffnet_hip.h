@@ -448,6 +448,23 @@ int dn_minplus_node_tile(void);
 int dn_minplus_sweeps_f64(const int32_t* rowptr, const int32_t* col, const double* w, int n_nodes, double* dist, int n_src, int n_sweeps,
                           int32_t* changed, void* stream);
 
+/* ---- Laplacian eigenbasis (geometry.laplacian_eigenbasis): one step of the Chebyshev recurrence on a block of vectors (dn_eigen.hip),
+ *      every product with S of the filtered subspace iteration.  rowptr [n_rows + 1], col [nnz] int32, val [nnz] fp64: S in CSR, columns in
+ *      [0, n_rows) (NOT checked here: the caller validates them).  Y, Z, out: fp64 row-major blocks [n_rows, ld] of which columns [0, nb)
+ *      are used, ld >= nb.
+ *          out[i][c] = alpha * sum_p val[p] * Y[col[p]][c]  +  beta * Y[i][c]  +  gamma * Z[i][c]     p in [rowptr[i], rowptr[i + 1])
+ *      (1, 0, 0) is S Y; (2 / e, -2 c / e, -1) with Z the block before last is one step of T_(j+1) = 2 ((S - c) / e) T_j - T_(j-1).
+ *      One fma per entry in CSR order, then alpha * sum, fma(beta, Y, .), fma(gamma, Z, .); no atomics: repeatable bit for bit.  A term
+ *      whose scalar is 0 is not formed and its operand not read: Z may be NULL when gamma == 0.  out may be Z (each element is read by the
+ *      lane that writes it); out must not be Y.  Columns [nb, ld) are never read from Y or Z and never written in out.  Any nb (64-column
+ *      tiles, lanes masked), any n_rows, empty rows and rows of any length.  No workspace, no allocation, no synchronisation.
+ *      dn_cheb_rows_per_workgroup(): the rows a workgroup owns (for tests of ragged sizes).
+ *      Returns 0 on success (n_rows == 0 or nb == 0: nothing is launched) and non-zero WITHOUT launching for a negative size, ld < nb, a
+ *      NULL rowptr, col, val, Y or out, a NULL Z with gamma != 0, out == Y, or nb > 65535 * 64. */
+int dn_cheb_rows_per_workgroup(void);
+int dn_cheb_step_f64(const int32_t* rowptr, const int32_t* col, const double* val, int n_rows, const double* Y, const double* Z, double* out,
+                     int nb, int ld, double alpha, double beta, double gamma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

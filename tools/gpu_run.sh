@@ -15,6 +15,8 @@
 #                script's row loop of torch.inverse, with launches per step (tools/fmap_timing.py)
 #   geodesic     all-pairs mesh distances at the FAUST size for n_steiner = 0, 1, 3: sweeps, time of a sweep and of the device route, scipy's
 #                Dijkstra scaled from 64 sources; the accuracy tables of the Steiner graph on the CPU route (tools/geodesic_timing.py)
+#   eigen        the Laplacian eigenbasis at 10 000 and 2 000 vertices, k_eig = 128: the device route end to end, one product with S, the shares
+#                of the dense products and of the host factorisations, eigsh on the same box -> eigenbasis_timing.txt (tools/eigen_timing.py)
 #   tests [k]    GPU parity tier (optionally -k <expr>)
 #   bench [args] bench.py (default flags: the timed steps only; add --full for the rest) -> $DN_OUT_DIR/bench.json
 #   prof         rocprofv3 --kernel-trace --stats of bench.py --full -> $DN_OUT_DIR/prof/
@@ -75,6 +77,8 @@ fmap)
   timeout 300 python tools/fmap_timing.py ;;
 geodesic)
   timeout 900 python tools/geodesic_timing.py "$@" ;;
+eigen)
+  timeout 420 python tools/eigen_timing.py ;;
 tests)
   if [ -n "$1" ]; then timeout 1500 python -m pytest tests/test_gpu_parity.py -m gpu -q --tb=short -x -k "$1" 2>&1 | tail -40 | tee $OUT/tests.txt
   else timeout 2400 python -m pytest tests -m gpu -q --tb=short -x 2>&1 | tail -40 | tee $OUT/tests.txt; fi ;;
