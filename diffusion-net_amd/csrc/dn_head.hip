@@ -69,14 +69,17 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a, int G) {
         if (a.labels) {
             const long long t = a.labels[ii];
             const bool valid = live && t >= 0 && t < a.C;
-            float at = 0.f, all = 0.f;
+            // the other classes are summed over c != t directly (no `all - at`: -inf - -inf, and a cancellation where |at| dominates), and
+            // not at all without smoothing: a masked class (-inf) outside the target must not reach the loss as 0 * -inf
+            const bool smooth = a.smoothing != 0.f;             // (uniform: the shuffles below run for every lane or for none)
+            float at = 0.f, oth = 0.f;
 #pragma unroll
-            for (int k = 0; k < CPL; ++k) if (gl + k * G < a.C) { all += z[k]; if (gl + k * G == t) at += z[k]; }
+            for (int k = 0; k < CPL; ++k) if (gl + k * G < a.C) { if (gl + k * G == t) at += z[k]; else if (smooth) oth += z[k]; }
             at = head_group_sum(at, G);
-            all = head_group_sum(all, G);
+            if (smooth) oth = head_group_sum(oth, G);
             if (valid && gl == 0) {
                 const float off = a.C > 1 ? a.smoothing / (float)(a.C - 1) : 0.f;
-                loss_sum -= (1.f - a.smoothing) * at + off * (all - at);
+                loss_sum -= smooth ? (1.f - a.smoothing) * at + off * oth : at;
                 cnt += 1.f;
             }
             if (live && !valid && t != DN_HEAD_IGNORE && gl == 0) loss_sum += __uint_as_float(0x7fc00000u);   // not a class, not ignore_index

@@ -21,7 +21,8 @@ def nll_loss(log_probs, labels):
     """Drop-in for ``torch.nn.functional.nll_loss(log_probs, labels)`` (mean reduction, rows x classes) on the HIP path: one pass over
     the log-probabilities forward, one backward (dn_head.hip).  Rows labelled -100 (torch's default ``ignore_index``) neither
     contribute nor count; any other label outside [0, C) makes the loss NaN (torch raises a device-side assert there; a NaN is as loud
-    and needs no host synchronisation).  Class weights and other reductions are not implemented (use torch); more than 2048 classes
+    and needs no host synchronisation).  A ``-inf`` log-probability (a masked class, ``log(0)``) counts only in the row whose label it is,
+    where the loss is ``+inf`` as in torch.  Class weights and other reductions are not implemented (use torch); more than 2048 classes
     fall back to ``torch.nn.functional.nll_loss``."""
     from . import _hip, ops
     if log_probs.dim() != 2:
@@ -36,7 +37,9 @@ def label_smoothing_log_loss(pred, labels, smoothing=0.0):
     smoothed one-hot target, mean over rows.  The reference builds its one-hot with ``one_hot[labels] = 1``, which is a
     proper one-hot only for the 1-D prediction of its single caller (classification_shrec11.py: one mesh, scalar label);
     that case is reproduced exactly, and 2-D predictions get the per-row one-hot the formula intends.  On a ROCm device the loss
-    and its gradient are one HIP kernel each (the NLL kernel with a smoothed target); host tensors use the torch formula."""
+    and its gradient are one HIP kernel each (the NLL kernel with a smoothed target); host tensors use the torch formula.  With
+    ``smoothing == 0`` the kernel never forms the off-target term, so a ``-inf`` log-probability outside the target gives the finite
+    NLL there, where the reference's literal formula yields NaN from ``0 * -inf``."""
     if pred.is_cuda and pred.dtype == torch.float32 and pred.dim() in (1, 2) and pred.shape[-1] <= 2048:
         from . import ops
         p2 = pred.reshape(1, -1) if pred.dim() == 1 else pred
