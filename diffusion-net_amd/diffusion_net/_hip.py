@@ -120,6 +120,11 @@ _SIGNATURES = {
     "dn_cloud_star_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [_vp] * 4),
     "dn_cloud_laplacian_emit_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
     "dn_segment_sum_f64_f32": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 5),
+    "dn_mesh_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dn_mesh_emit_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "dn_segment_sum_f64_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 5),
+    "dn_segment_sum4_f64_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "dn_mesh_frames_gradients_f64": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int] + [_vp] * 6),
     "dn_fmap_max_k": (C.c_int, []),
     "dn_fmap_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "dn_fmap_solve_fwd_f32": (C.c_int, [_vp] * 4 + [C.c_int] * 3 + [C.c_float, _vp, _vp, C.c_size_t, _vp, _vp]),

@@ -8,6 +8,8 @@ The host-side operator precompute keeps the reference's names here (``compute_op
 point-cloud operators: ``vertex_normals``, ``build_tangent_frames``, ``build_grad_point_cloud`` (the reference's names) and
 ``cloud_operators`` (normals, frames and gradient stencils of a cloud in one HIP pass over its neighbour table);
 ``point_cloud_laplacian`` is the local-Delaunay Laplacian and mass of a cloud (dn_cloud_lap.hip on the device).
+``mesh_operators`` assembles what a triangle mesh needs in front of the eigenproblem -- frames, mass, cotan Laplacian, gradient operator
+-- on the device (dn_mesh.hip); ``compute_operators_via(..., assembly="device")`` builds the seven operators on it.
 ``geodesic_label_errors`` and ``get_all_pairs_geodesic_distance`` are the evaluation metric of the correspondence experiments: all-pairs
 distances on the mesh's Steiner-point graph (``mesh_distance_graph``, ``geodesic_distances``), swept on the device by dn_geodesic.hip.
 """
@@ -18,7 +20,7 @@ import torch
 from . import ops
 from .batch import MeshBatch
 from .precompute import compute_operators, get_all_operators, get_operators, neighborhood_normal, normalize_positions  # noqa: F401
-from .precompute import compute_operators_with  # noqa: F401
+from .precompute import compute_operators_via, compute_operators_with  # noqa: F401
 from . import precompute as _pre
 
 
@@ -294,6 +296,71 @@ def point_cloud_laplacian(verts, n_neighbors=30, frames=None):
         return _laplacian_of_table(verts, nbr, frames)
     L, mass = _pre.point_cloud_laplacian_host(verts.detach().cpu().numpy(), n_neighbors, frames)
     return _pre._to_torch_sparse(L, verts.device, verts.dtype), torch.from_numpy(mass).to(device=verts.device, dtype=verts.dtype)
+
+
+# ----------------------------------------------------------------------------------------------
+# triangle meshes: cotan Laplacian, mass, frames, gradient operator (geometry.py:114-177, 209-273, 306-335) on the device (dn_mesh.hip)
+# ----------------------------------------------------------------------------------------------
+def _mesh_on_device(verts):
+    """fp32 positions on a ROCm device: ``ops.mesh_assemble`` + ``ops.mesh_frames_gradients``.  (Host tensors take this route only while
+    the test suite has bound the emulator build of the library, which runs the same kernels on host buffers.)"""
+    return (verts.is_cuda or ops._hip._allow_host_tensors) and verts.dtype == torch.float32
+
+
+def _mesh_operators_fp64(verts, faces, normals=None):
+    """The device route of ``mesh_operators`` in fp64, before any cast: (rowptr [V + 1] int32, col [nnz] int32, lval [nnz], mass [V],
+    frames [V, 3, 3], gx [nnz], gy [nnz]) on the device of ``verts``; L, gradX and gradY share the pattern."""
+    dev = verts.device
+    faces = faces.to(device=dev, dtype=torch.int64)
+    rowptr, col, lval, mass, nsum = ops.mesh_assemble(verts, faces)
+    if normals is not None:
+        n64 = normals.to(device=dev, dtype=torch.float64)
+    else:
+        n64 = nsum / torch.linalg.vector_norm(nsum, dim=1, keepdim=True)
+        if not bool(torch.isfinite(n64).all()):
+            # an unreferenced vertex, opposing faces: the reference's jitter-and-fixed-direction rule re-estimates the neighbours too, so
+            # the normals of the whole mesh come from the host function that states it
+            import numpy as np
+            n = _pre.vertex_normals(verts.detach().cpu().numpy().astype(np.float64), faces.detach().cpu().numpy())
+            n64 = torch.from_numpy(np.ascontiguousarray(n)).to(dev)
+    frames, gx, gy = ops.mesh_frames_gradients(verts, rowptr, col, n64.contiguous())
+    if bool(torch.isnan(frames).any()):
+        raise ValueError("NaN coordinate frame! Must be very degenerate")
+    return rowptr, col, lval, mass, frames, gx, gy
+
+
+def _csr_rows(rowptr, n_entries):
+    counts = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
+    return torch.repeat_interleave(torch.arange(counts.numel(), device=rowptr.device), counts, output_size=n_entries)
+
+
+def mesh_operators(verts, faces, normals=None):
+    """Frames, lumped mass, cotan Laplacian and gradient operator of a triangle mesh: ``(frames [V,3,3], massvec [V], L, gradX, gradY)``,
+    L / gradX / gradY coalesced sparse COO [V,V], all on the device and in the dtype of ``verts`` -- what ``compute_operators`` assembles
+    in front of the eigenproblem (``massvec`` is the raw mass, without its EPS x mean).  ``normals`` [V,3]: use these (cast to fp64)
+    instead of the normalised sums of the unit face normals.
+
+    fp32 positions on a ROCm device run ``ops.mesh_assemble`` and ``ops.mesh_frames_gradients`` (dn_mesh.hip): fp64 inside, rounded
+    once; gradX and gradY stand on L's own pattern (explicit zeros included).  If a vertex has no finite normal (unreferenced, opposing
+    faces) the normals of the whole mesh are taken from ``precompute.vertex_normals`` on the host, which states the reference's rule for
+    them.  Everything else (host tensors, fp64) takes the host functions of ``precompute`` in fp64.  NaN frames: ``ValueError``."""
+    V = verts.shape[0]
+    if _mesh_on_device(verts):
+        rowptr, col, lval, mass, frames, gx, gy = _mesh_operators_fp64(verts, faces, normals)
+        idx = torch.stack((_csr_rows(rowptr, col.numel()), col.to(torch.int64)))
+        sparse = lambda v: torch.sparse_coo_tensor(idx, v.to(verts.dtype), (V, V), is_coalesced=True)
+        return frames.to(verts.dtype), mass.to(verts.dtype), sparse(lval), sparse(gx), sparse(gy)
+    import numpy as np
+    v = verts.detach().cpu().numpy().astype(np.float64)
+    f = faces.detach().cpu().numpy().astype(np.int64)
+    n = _pre.vertex_normals(v, f) if normals is None else normals.detach().cpu().numpy().astype(np.float64)
+    frames = _pre.tangent_frames(n)
+    L = _pre.cotan_laplacian(v, f, denom_eps=1e-10)
+    Lc = L.tocoo()
+    grad = _pre.gradient_operator(v, frames, np.stack([Lc.row, Lc.col]))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=verts.device, dtype=verts.dtype)
+    sp = lambda m: _pre._to_torch_sparse(m, verts.device, verts.dtype)
+    return t(frames), t(_pre.vertex_areas(v, f)), sp(L), sp(grad.real), sp(grad.imag)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -390,6 +390,136 @@ def cloud_laplacian(points, nbr, frames):
 
 
 # ----------------------------------------------------------------------------------------------
+# triangle-mesh operators: cotan Laplacian, mass, normal sums, frames, gradients (include/diffnet_hip.h: dn_mesh_emit_f32)
+# ----------------------------------------------------------------------------------------------
+@_on_device
+def _mesh_assemble_launch(verts, faces):
+    """Every device step of ``mesh_assemble`` without a host read: emit, stable sort of the keys (torch), segment sums.
+    -> (rowptr [V + 1] int32, col, lval [9 F] (the first ``count`` entries are the matrix; fp64), vrec [V, 4] fp64 (mass, normal sum),
+    count [1] int32, status [1] int32)."""
+    L = _hip.lib()
+    V, F = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    m = 9 * F
+    st = _hip.stream_of(verts)
+    rowptr = torch.zeros(V + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    lval = torch.empty(max(m, 1), dtype=torch.float64, device=dev)
+    vrec = torch.zeros(V, 4, dtype=torch.float64, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if F == 0:
+        return rowptr, col[:0], lval[:0], vrec, count, status
+    ws = _hip.workspace(dev, L.dn_mesh_workspace_bytes(V, F))
+    _hip.check(L.dn_mesh_emit_f32(verts.data_ptr(), V, faces.data_ptr(), F, ws.data_ptr(), ws.numel(), status.data_ptr(), st), "dn_mesh_emit_f32")
+    # the workspace layout of include/diffnet_hip.h
+    Fe = (F + 1) // 2 * 2
+    key_l, val_l = ws[:72 * F].view(torch.int64), ws[72 * Fe:72 * Fe + 72 * F].view(torch.float64)
+    key_v, val_v = ws[144 * Fe:144 * Fe + 24 * F].view(torch.int64), ws[168 * Fe:168 * Fe + 96 * F].view(torch.float64)
+    skey, perm = torch.sort(key_l, stable=True)
+    head = torch.ones(m, dtype=torch.bool, device=dev)
+    torch.ne(skey[1:], skey[:-1], out=head[1:])
+    rank = torch.cumsum(head, 0, dtype=torch.int64)
+    _hip.check(L.dn_segment_sum_f64_f64(skey.data_ptr(), perm.data_ptr(), val_l.data_ptr(), m, rank.data_ptr(), V, rowptr.data_ptr(),
+                                        col.data_ptr(), lval.data_ptr(), count.data_ptr(), st), "dn_segment_sum_f64_f64")
+    if V:                                     # (no vertex: every face is out of range and the status word says so)
+        skey_v, perm_v = torch.sort(key_v, stable=True)
+        _hip.check(L.dn_segment_sum4_f64_f64(skey_v.data_ptr(), perm_v.data_ptr(), val_v.data_ptr(), 3 * F, V, vrec.data_ptr(), st),
+                   "dn_segment_sum4_f64_f64")
+    return rowptr, col, lval, vrec, count, status
+
+
+def _mesh_check_verts(verts, what):
+    _hip.require_device(verts)
+    verts = _f32c(verts)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("%s takes [V, 3] vertex positions (got %s)" % (what, tuple(verts.shape)))
+    if verts.shape[0] > 2 ** 31 - 1:
+        raise ValueError("%s: %d vertices do not fit a 32-bit index" % (what, verts.shape[0]))
+    return verts
+
+
+def mesh_assemble(verts, faces):
+    """Cotan Laplacian, lumped mass and vertex normal sums of a triangle mesh (geometry.py:114-148, 306-335; include/diffnet_hip.h:
+    dn_mesh_emit_f32), forward only.  ``verts`` [V, 3] fp32, ``faces`` [F, 3] int64.
+    -> (rowptr [V + 1] int32, col [nnz] int32, lval [nnz] fp64, mass [V] fp64, normal_sum [V, 3] fp64): L is CSR with ascending columns,
+    per corner w = 0.5 (a.b) / (|a x b| + 1e-10) (explicit zeros stay entries), symmetric bit for bit; the mass is a third of the area of
+    the incident faces, ``normal_sum`` the sum of their n / (|n| + 1e-6).  fp64 from the coordinate differences on, no floating-point
+    atomics: the result repeats bit for bit from call to call.  Raises ``IndexError`` if a face holds an index outside [0, V) (reading
+    the status word and the number of entries waits for the kernels)."""
+    verts = _mesh_check_verts(verts, "mesh_assemble")
+    _hip.require_device(faces)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("mesh_assemble takes [F, 3] faces (got %s)" % (tuple(faces.shape),))
+    if faces.dtype != torch.int64:
+        raise TypeError("mesh_assemble takes int64 faces (got %s)" % faces.dtype)
+    if faces.device != verts.device:
+        raise RuntimeError("mesh_assemble: vertices on %s, faces on %s" % (verts.device, faces.device))
+    V, F = verts.shape[0], faces.shape[0]
+    if 9 * F > 2 ** 31 - 1:
+        raise ValueError("mesh_assemble: 9 x %d matrix terms do not fit a 32-bit count" % F)
+    rowptr, col, lval, vrec, count, status = _mesh_assemble_launch(verts, faces.contiguous())
+    bad, nnz = torch.cat((status, count)).tolist()
+    if bad:
+        raise IndexError("mesh_assemble: %d face(s) hold an index outside [0, %d)" % (bad, V))
+    return rowptr, col[:nnz].clone(), lval[:nnz].clone(), vrec[:, 0].contiguous(), vrec[:, 1:].contiguous()
+
+
+@_on_device
+def _mesh_frames_gradients_launch(verts, rowptr, col, normals):
+    """The vertex pass without a host read -> (frames [V, 3, 3], gx [nnz], gy [nnz] fp64, status [1] int32)."""
+    V, nnz = verts.shape[0], col.numel()
+    dev = verts.device
+    frames = torch.empty(V, 3, 3, dtype=torch.float64, device=dev)
+    gx = torch.zeros(nnz, dtype=torch.float64, device=dev)
+    gy = torch.zeros(nnz, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if V == 0:
+        return frames, gx, gy, status
+    _hip.check(_hip.lib().dn_mesh_frames_gradients_f64(verts.data_ptr(), V, rowptr.data_ptr(), _hip.ptr(col) if nnz else None, nnz,
+                                                       normals.data_ptr(), frames.data_ptr(), _hip.ptr(gx) if nnz else None,
+                                                       _hip.ptr(gy) if nnz else None, status.data_ptr(), _hip.stream_of(verts)),
+               "dn_mesh_frames_gradients_f64")
+    return frames, gx, gy, status
+
+
+def _mesh_check_pattern(verts, rowptr, col, normals, what="mesh_frames_gradients"):
+    verts = _mesh_check_verts(verts, what)
+    for t in (rowptr, col, normals):
+        _hip.require_device(t)
+    V = verts.shape[0]
+    if rowptr.dtype != torch.int32 or col.dtype != torch.int32:
+        raise TypeError("%s takes int32 rowptr and col (got %s, %s)" % (what, rowptr.dtype, col.dtype))
+    if normals.dtype != torch.float64:
+        raise TypeError("%s takes fp64 normals (got %s)" % (what, normals.dtype))
+    if rowptr.dim() != 1 or rowptr.numel() != V + 1 or col.dim() != 1:
+        raise ValueError("%s takes CSR arrays rowptr [V + 1], col [nnz] for [V, 3] positions (got %s, %s for %s)"
+                         % (what, tuple(rowptr.shape), tuple(col.shape), tuple(verts.shape)))
+    if tuple(normals.shape) != (V, 3):
+        raise ValueError("%s takes [V, 3] normals (got %s)" % (what, tuple(normals.shape)))
+    if not (rowptr.device == col.device == normals.device == verts.device):
+        raise RuntimeError("%s: vertices on %s, rowptr on %s, col on %s, normals on %s" % (what, verts.device, rowptr.device, col.device, normals.device))
+    if col.numel() > 2 ** 31 - 1:
+        raise ValueError("%s: %d entries do not fit a 32-bit row pointer" % (what, col.numel()))
+    return verts, rowptr.contiguous(), col.contiguous(), normals.contiguous()
+
+
+def mesh_frames_gradients(verts, rowptr, col, normals):
+    """Tangent frames of given normals and the least-squares gradient operator on a CSR pattern -- L's own, as ``mesh_assemble`` returns
+    it (geometry.py:151-177, 209-273; include/diffnet_hip.h: dn_mesh_frames_gradients_f64), forward only.  ``verts`` [V, 3] fp32,
+    ``rowptr`` [V + 1] and ``col`` [nnz] int32, ``normals`` [V, 3] fp64.
+    -> (frames [V, 3, 3] fp64, gx [nnz] fp64, gy [nnz] fp64): row i of gx + i gy is the stencil of vertex i over the off-diagonal entries
+    of its row, its own coefficient in the diagonal entry.  Raises ``IndexError`` if a row pointer or a column is out of range or a
+    non-empty row has no diagonal entry (reading the status word waits for the kernel)."""
+    verts, rowptr, col, normals = _mesh_check_pattern(verts, rowptr, col, normals)
+    frames, gx, gy, status = _mesh_frames_gradients_launch(verts, rowptr, col, normals)
+    bad = int(status.item())
+    if bad:
+        raise IndexError("mesh_frames_gradients: %d row(s) of the pattern are out of range or lack their diagonal entry" % bad)
+    return frames, gx, gy
+
+
+# ----------------------------------------------------------------------------------------------
 # all-pairs graph distances: (min, +) relaxation sweeps (include/diffnet_hip.h: dn_minplus_sweeps_f64)
 # ----------------------------------------------------------------------------------------------
 @_on_device

@@ -351,6 +351,14 @@ def _check_eigensolver(eigensolver):
         raise ValueError("eigensolver=%r: None (shift-invert eigsh) or \"subspace\"" % (eigensolver,))
 
 
+ASSEMBLIES = (None, "device")
+
+
+def _check_assembly(assembly):
+    if assembly not in ASSEMBLIES:
+        raise ValueError("assembly=%r: None (the host functions of this module) or \"device\"" % (assembly,))
+
+
 # ----------------------------------------------------------------------------------------- point-cloud Laplacian (local Delaunay stars)
 STAR_CR_TOL = 1e-12   # |cross(a, b)| <= STAR_CR_TOL sqrt(W_a W_b): a, b and the centre are collinear (dn_cloud_lap.hip: LP_CR_TOL)
 
@@ -557,18 +565,56 @@ def compute_operators(verts, faces, k_eig, normals=None, *, laplacian=None):
     return compute_operators_with(verts, faces, k_eig, normals, laplacian=laplacian, eigensolver=None)
 
 
+def _compute_mesh_operators_device(verts, faces, k_eig, normals, eigensolver):
+    """The mesh branch of ``compute_operators_via`` under ``assembly="device"``: normals, frames, L, mass and the gradient operator by
+    ``geometry._mesh_operators_fp64`` (dn_mesh.hip); the eigenproblem gets the fp64 CSR and mass, downloaded once."""
+    from . import geometry                         # (geometry imports this module)
+    device, dtype = verts.device, verts.dtype
+    V = verts.shape[0]
+    rowptr, col, lval, mass_t, frames, gx, gy = geometry._mesh_operators_fp64(verts, faces, normals)
+    mass_t = mass_t + EPS * mass_t.mean()
+    L = sp.csr_matrix((lval.cpu().numpy(), col.cpu().numpy(), rowptr.cpu().numpy()), shape=(V, V))
+    mass = mass_t.cpu().numpy()
+    if np.isnan(L.data).any():
+        raise RuntimeError("NaN Laplace matrix")
+    if np.isnan(mass).any():
+        raise RuntimeError("NaN mass matrix")
+    evals, evecs = _eigenbasis(L, mass, k_eig, eigensolver, device)
+    idx = torch.stack((geometry._csr_rows(rowptr, col.numel()), col.to(torch.int64)))
+    sparse = lambda v: torch.sparse_coo_tensor(idx, v.to(dtype), (V, V), is_coalesced=True)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)
+    return frames.to(dtype), mass_t.to(dtype), sparse(lval), t(evals), t(evecs), sparse(gx), sparse(gy)
+
+
 def compute_operators_with(verts, faces, k_eig, normals=None, *, laplacian=None, eigensolver=None):
     """``compute_operators`` with the choice of the eigensolver (``get_operators`` and ``get_all_operators`` take the same keyword and pass it
     here).  ``eigensolver``: None -- shift-invert ``eigsh`` on the host, as the reference -- or ``"subspace"``:
     ``geometry.laplacian_eigenbasis``, Chebyshev-filtered subspace iteration whose products run on the device (dn_eigen.hip) where there is
     one, for meshes and for both point-cloud branches alike.  The pairs solve the same pencil to ``rtol = 1e-9``; the eigenvectors differ by
-    sign (and by a rotation inside a repeated eigenvalue), the six other outputs are identical.  Anything else: ``ValueError``."""
+    sign (and by a rotation inside a repeated eigenvalue), the six other outputs are identical.  Anything else: ``ValueError``.
+    (This function keeps the parameter list it has had, as ``compute_operators`` did: ``compute_operators_via`` adds ``assembly``.)"""
+    return compute_operators_via(verts, faces, k_eig, normals, laplacian=laplacian, eigensolver=eigensolver, assembly=None)
+
+
+def compute_operators_via(verts, faces, k_eig, normals=None, *, laplacian=None, eigensolver=None, assembly=None):
+    """``compute_operators_with`` with the choice of where a mesh is assembled (``get_operators`` and ``get_all_operators`` take the same
+    keyword and pass it here).  ``assembly``: None -- the normals, frames, cotan Laplacian, mass and gradient operator of a MESH come from the fp64 host functions of
+    this module and are uploaded -- or ``"device"``: fp32 positions on a ROCm device are assembled there by the kernels of dn_mesh.hip
+    (``geometry.mesh_operators``: fp64 inside, no floating-point atomics, the gradient operator on L's own pattern); the eigenproblem gets
+    the fp64 L and mass, downloaded once, and the seven outputs are rounded to the dtype of ``verts`` once.  The two routes sum the same
+    terms in another order: they agree to fp64 round-off before that rounding.  Without a device, and for positions that are not fp32,
+    ``"device"`` is the host route; a point cloud (empty ``faces``) chooses its own route either way.  Anything else: ``ValueError``."""
     _check_eigensolver(eigensolver)
+    _check_assembly(assembly)
     device, dtype = verts.device, verts.dtype
     if faces.numel() == 0:
         return _compute_cloud_operators(verts, k_eig, normals, laplacian, eigensolver=eigensolver)
     if laplacian is not None:
         raise ValueError("laplacian= is for point clouds (empty faces); a triangle mesh gets its cotan Laplacian")
+    if assembly == "device":
+        from . import geometry                     # (geometry imports this module)
+        if geometry._mesh_on_device(verts):
+            return _compute_mesh_operators_device(verts, faces, k_eig, normals, eigensolver)
     v = verts.detach().cpu().numpy().astype(np.float64)
     f = faces.detach().cpu().numpy().astype(np.int64)
     n = vertex_normals(v, f) if normals is None else normals.detach().cpu().numpy().astype(np.float64)
@@ -593,15 +639,19 @@ def _sparse_to_csc(t):
     return sp.coo_matrix((val, (idx[0], idx[1])), shape=tuple(t.shape)).tocsc()
 
 
-def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, overwrite_cache=False, *, laplacian=None, eigensolver=None):
+def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, overwrite_cache=False, *, laplacian=None, eigensolver=None,
+                  assembly=None):
     """``compute_operators`` behind the reference's on-disk npz cache (geometry.py:426-570): same key derivation, same
     file names, same array names (float32 payload, CSC triplets for L / gradX / gradY), so either implementation can
     read the other's cache.  A hit is verified against the stored verts/faces; an entry with too few eigenpairs is
     rebuilt.  ``laplacian``: passed on to ``compute_operators`` (point clouds).  The key is the reference's -- positions and faces only --
     so a hit cannot tell which Laplacian wrote the entry: a cache directory should be filled with one ``laplacian`` choice.
     ``eigensolver``: None or "subspace" (``compute_operators_with``); it is not part of the key either, so the same holds: a cache directory
-    should be filled with one ``eigensolver`` choice."""
+    should be filled with one ``eigensolver`` choice.
+    ``assembly``: None or "device" (``compute_operators_via``: where a mesh's operators are assembled).  It is not part of the key either;
+    the two routes agree to fp64 round-off before the fp32 payload is written, so an entry of one serves the other."""
     _check_eigensolver(eigensolver)
+    _check_assembly(assembly)
     device, dtype = verts.device, verts.dtype
     v_np, f_np = verts.detach().cpu().numpy(), faces.detach().cpu().numpy()
     if np.isnan(v_np).any():
@@ -630,10 +680,12 @@ def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, over
                         _to_torch_sparse(rd("gradY"), device, dtype))
             except Exception:              # unreadable entry: rebuild in place  # noqa: BLE001
                 break
-    if eigensolver is None:
+    if eigensolver is None and assembly is None:
         out = compute_operators(verts, faces, k_eig, normals=normals, laplacian=laplacian)
-    else:
+    elif assembly is None:
         out = compute_operators_with(verts, faces, k_eig, normals=normals, laplacian=laplacian, eigensolver=eigensolver)
+    else:
+        out = compute_operators_via(verts, faces, k_eig, normals=normals, laplacian=laplacian, eigensolver=eigensolver, assembly=assembly)
     if path is not None:
         frames, mass, L, evals, evecs, gX, gY = out
         f32 = lambda a: a.detach().cpu().numpy().astype(np.float32)
@@ -646,14 +698,16 @@ def get_operators(verts, faces, k_eig=128, op_cache_dir=None, normals=None, over
     return out
 
 
-def get_all_operators(verts_list, faces_list, k_eig, op_cache_dir=None, normals=None, *, laplacian=None, eigensolver=None):
+def get_all_operators(verts_list, faces_list, k_eig, op_cache_dir=None, normals=None, *, laplacian=None, eigensolver=None, assembly=None):
     """Lists in, seven lists out (geometry.py:395-424).  ``laplacian``: None, one value for every entry, or a list with one per entry.
-    ``eigensolver``: one value for every entry (``compute_operators_with``)."""
+    ``eigensolver``, ``assembly``: one value for every entry (``compute_operators_with``, ``compute_operators_via``)."""
     _check_eigensolver(eigensolver)
+    _check_assembly(assembly)
     cols = [[] for _ in range(7)]
     for i, (v, f) in enumerate(zip(verts_list, faces_list)):
         lap = laplacian[i] if isinstance(laplacian, list) else laplacian
-        res = get_operators(v, f, k_eig, op_cache_dir, normals=None if normals is None else normals[i], laplacian=lap, eigensolver=eigensolver)
+        res = get_operators(v, f, k_eig, op_cache_dir, normals=None if normals is None else normals[i], laplacian=lap, eigensolver=eigensolver,
+                            assembly=assembly)
         for c, r in zip(cols, res):
             c.append(r)
     return tuple(cols)

@@ -313,6 +313,31 @@ def _(points, nbr, frames):
             points.new_empty(nnz, dtype=torch.float32), points.new_empty(n, dtype=torch.float32))
 
 
+# ------------------------------------------------------------------------------------------------ triangle-mesh operators (forward only)
+@_op("diffusion_net::mesh_assemble")
+def mesh_assemble(verts: Tensor, faces: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return ops.mesh_assemble(verts, faces)
+
+
+@mesh_assemble.register_fake
+def _(verts, faces):
+    V = verts.shape[0]
+    nnz = torch.library.get_ctx().new_dynamic_size()       # the number of entries depends on the data
+    return (verts.new_empty(V + 1, dtype=torch.int32), verts.new_empty(nnz, dtype=torch.int32), verts.new_empty(nnz, dtype=torch.float64),
+            verts.new_empty(V, dtype=torch.float64), verts.new_empty(V, 3, dtype=torch.float64))
+
+
+@_op("diffusion_net::mesh_frames_gradients")
+def mesh_frames_gradients(verts: Tensor, rowptr: Tensor, col: Tensor, normals: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    return ops.mesh_frames_gradients(verts, rowptr, col, normals)
+
+
+@mesh_frames_gradients.register_fake
+def _(verts, rowptr, col, normals):
+    V, nnz = verts.shape[0], col.shape[0]
+    return (verts.new_empty(V, 3, 3, dtype=torch.float64), verts.new_empty(nnz, dtype=torch.float64), verts.new_empty(nnz, dtype=torch.float64))
+
+
 # ------------------------------------------------------------------------------------------------ functional maps (regularised spectral solve)
 @_op("diffusion_net::fmap_solve")
 def fmap_solve(A: Tensor, B: Tensor, evals_x: Tensor, evals_y: Tensor, lam: float) -> Tensor:

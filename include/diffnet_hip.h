@@ -404,6 +404,47 @@ int dn_cloud_laplacian_emit_f32(const float* pts, int n, const int64_t* nbr, int
 int dn_segment_sum_f64_f32(const int64_t* keys, const int64_t* perm, const double* vals, int m, const int64_t* rank, int n_rows,
                            int32_t* rowptr, int32_t* col, float* out, int32_t* count, void* stream);
 
+/* ---- triangle-mesh operators (geometry.py:114-148, 151-177, 209-273, 306-335 for a mesh; dn_mesh.hip): cotan Laplacian, lumped mass,
+ *      vertex normal sums, tangent frames and the least-squares gradient operator.  verts [n_verts,3] fp32; faces [n_faces,3] int64.
+ *        emit    dn_mesh_emit_f32, one lane per face (v0, v1, v2).  Per corner o with opposite edge (i, j): a = x_i - x_o, b = x_j - x_o,
+ *                w_o = 0.5 (a.b) / (|a x b| + 1e-10); the edge gets -w_o on its two off-diagonals and +w_o on its two diagonals.  Every
+ *                vertex of the face gets a record (area / 3, n / (|n| + 1e-6)) with n = (x_1 - x_0) x (x_2 - x_0), area = |n| / 2 (the
+ *                reference's normalize(): deliberately not quite unit).  Written to the workspace, dn_mesh_workspace_bytes(n_verts,
+ *                n_faces) = 264 Fe bytes with Fe = n_faces rounded up to even (every array starts on a 16-byte boundary):
+ *                  int64 key_l [9 F] at byte 0, fp64 val_l [9 F] at 72 Fe, int64 key_v [3 F] at 144 Fe, fp64 val_v [3 F, 4] at 168 Fe;
+ *                face f owns entries 9 f .. 9 f + 8 of L -- keys (row << 32 | col): the diagonals of v0, v1, v2 (each the sum of its two
+ *                edge weights: w_1 + w_2, w_2 + w_0, w_0 + w_1), then (v1,v2) (v2,v1) with -w_0, (v2,v0) (v0,v2) with -w_1, (v0,v1)
+ *                (v1,v0) with -w_2 -- and records 3 f .. 3 f + 2 (keys v0, v1, v2, four values each: area / 3 and the unit normal).
+ *                A face that repeats an index emits its terms as the formulas give them (a = 0, so w = 0): explicit zeros stay entries.
+ *                status: one device int32, set to the number of faces that hold an index outside [0, n_verts); such a face reads nothing
+ *                through it and writes the key INT64_MAX, which sorts last, and zeros.  The caller reads the word at its next
+ *                synchronisation point.
+ *        sum     dn_segment_sum_f64_f64: dn_segment_sum_f64_f32 with an fp64 `out` -- every run of equal keys (sorted ascending by a
+ *                STABLE sort) other than INT64_MAX is added in sorted order in fp64 and stored as it is; rowptr != NULL: CSR with ascending
+ *                columns (rank, col, count as there), rowptr == NULL: keys index out [n_rows], zeroed first.  dn_segment_sum4_f64_f64:
+ *                the dense form for FOUR values per key, vals [m, 4] (unsorted) -> out [n_rows, 4]: the records of the vertices.
+ *        vertex  dn_mesh_frames_gradients_f64, one lane per row of a CSR pattern (rowptr [n_verts + 1], col [nnz], int32; L's own) with
+ *                normals [n_verts,3] fp64.  frames [n_verts,3,3] fp64, rows basisX, basisY, normal: basisX = c - n (n.c) with c = e_x where
+ *                |n_x| < 0.9, else e_y, divided by (|basisX| + 1e-6); basisY = n x basisX.  Over the off-diagonal entries j of row i in
+ *                column order: t_j = ((x_j - x_i).basisX, (x_j - x_i).basisY), G = sum_j t_j t_j^T + 1e-5 I; gx [nnz], gy [nnz] fp64 on
+ *                the same pattern get G^-1 t_j at entry j and -sum_j G^-1 t_j at the diagonal entry.  An empty row writes its frame only.
+ *                status: one device int32, set to the number of rows with a row pointer outside [0, nnz] or decreasing (nothing is walked),
+ *                a column outside [0, n_verts) (its entry gets 0 and takes no part) or, if not empty, no diagonal entry.
+ *      Everything from the coordinate differences on is fp64.  No floating-point atomics: every sum runs in the sorted order -- face
+ *      after face, a face's terms in the order above -- so the result is bit-identical from run to run, and L[i,j] and L[j,i] are sums
+ *      of the same terms in the same order: the same bits.
+ *      Each returns 0 on success (n_faces == 0, n_verts == 0 with nnz == 0, or m == 0 and n_rows == 0: nothing is launched and nothing
+ *      is written, the status word included) and non-zero WITHOUT launching for n_verts < 0, n_faces < 0, 9 n_faces > INT32_MAX (the query
+ *      returns 0 bytes for these), nnz < 0, nnz > 0 with n_verts == 0, m < 0, n_rows < 0, a workspace smaller than the query says, or a
+ *      NULL pointer that the call would use. */
+size_t dn_mesh_workspace_bytes(int n_verts, int n_faces);
+int dn_mesh_emit_f32(const float* verts, int n_verts, const int64_t* faces, int n_faces, void* ws, size_t ws_bytes, int32_t* status, void* stream);
+int dn_segment_sum_f64_f64(const int64_t* keys, const int64_t* perm, const double* vals, int m, const int64_t* rank, int n_rows,
+                           int32_t* rowptr, int32_t* col, double* out, int32_t* count, void* stream);
+int dn_segment_sum4_f64_f64(const int64_t* keys, const int64_t* perm, const double* vals, int m, int n_rows, double* out, void* stream);
+int dn_mesh_frames_gradients_f64(const float* verts, int n_verts, const int32_t* rowptr, const int32_t* col, int nnz, const double* normals,
+                                 double* frames, double* gx, double* gy, int32_t* status, void* stream);
+
 /* ---- functional maps (experiments/functional_correspondence/fmaps_model.py:11-40): the regularised spectral solve and its backward
  *      (dn_fmap.hip).  A, B [P, K, F] fp32 row-major: the spectral coefficients of the features of shapes x and y of P pairs;
  *      evals_x, evals_y [P, K] fp32; lam: the regularisation weight.  With G = A A^T, H = B A^T and

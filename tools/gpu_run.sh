@@ -17,6 +17,9 @@
 #                Dijkstra scaled from 64 sources; the accuracy tables of the Steiner graph on the CPU route (tools/geodesic_timing.py)
 #   eigen        the Laplacian eigenbasis at 10 000 and 2 000 vertices, k_eig = 128: the device route end to end, one product with S, the shares
 #                of the dense products and of the host factorisations, eigsh on the same box -> eigenbasis_timing.txt (tools/eigen_timing.py)
+#   mesh         the assembly of a mesh's operators (normals, frames, cotan Laplacian, mass, gradient operator) at 10 000 and 200 000 vertices:
+#                geometry.mesh_operators on the device against the host functions on the same box, the device steps one by one
+#                -> mesh_operators_timing.txt (tools/mesh_operators_timing.py)
 #   tests [k]    GPU parity tier (optionally -k <expr>)
 #   bench [args] bench.py (default flags: the timed steps only; add --full for the rest) -> $DN_OUT_DIR/bench.json
 #   prof         rocprofv3 --kernel-trace --stats of bench.py --full -> $DN_OUT_DIR/prof/
@@ -79,6 +82,8 @@ geodesic)
   timeout 900 python tools/geodesic_timing.py "$@" ;;
 eigen)
   timeout 420 python tools/eigen_timing.py ;;
+mesh)
+  timeout 420 python tools/mesh_operators_timing.py ;;
 tests)
   if [ -n "$1" ]; then timeout 1500 python -m pytest tests/test_gpu_parity.py -m gpu -q --tb=short -x -k "$1" 2>&1 | tail -40 | tee $OUT/tests.txt
   else timeout 2400 python -m pytest tests -m gpu -q --tb=short -x 2>&1 | tail -40 | tee $OUT/tests.txt; fi ;;
