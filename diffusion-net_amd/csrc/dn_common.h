@@ -631,6 +631,12 @@ int dn_launch_hks(const float* evals, const float* evecs, const float* scales, i
 // exact k-nearest-neighbour search (dn_knn.hip): n_split target slices of tiles_per_slice 64-target tiles each; pk / pi [n_split][k][n_src] when n_split > 1
 int dn_launch_knn(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int largest, int omit_diagonal, int n_split,
                   int tiles_per_slice, float* dist, long long* idx, float* pk, int* pi, hipStream_t stream);
+// farthest point sampling (dn_fps.hip): the whole sample loop in one launch (clouds up to dn_fps_resident_max_points()), or one launch per
+// sample with min_d [n_clouds][G * 1024] and the per-workgroup partials pkey / pxyz [2][n_clouds][G] in the workspace
+int dn_launch_fps_resident(const float* pts, const long long* offsets, int n_clouds, int max_points, int n_sample, const long long* start,
+                           long long* order, float* radii, float* min_dist2, hipStream_t stream);
+int dn_launch_fps_stepped(const float* pts, const long long* offsets, int n_clouds, int max_points, int n_sample, const long long* start,
+                          float* md, void* pkey, void* pxyz, long long* order, float* radii, float* min_dist2, hipStream_t stream);
 // COO -> CSR + CSR of the transpose (dn_pack.hip).  rows == nullptr: entry j belongs to row j / row_div (gather patterns)
 size_t dn_pack_ws_bytes(long long nnz, int n_cols);
 int dn_launch_coo_to_csr(const long long* rows, int row_div, const long long* cols, const float* vx, const float* vy, long long nnz, int n_rows,

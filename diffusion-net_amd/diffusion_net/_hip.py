@@ -16,6 +16,7 @@ MAX_MLP = 8
 BLOCK_AMAX_WORDS = 16       # include/diffnet_hip.h: DN_BLOCK_AMAX_WORDS
 HEAD_MAX_CLASSES = 2048   # dn_head.hip: 64 lanes x DN_HEAD_CPL classes per row
 KNN_MAX_K = 32            # include/diffnet_hip.h: DN_KNN_MAX_K
+FPS_RESIDENT_MAX_POINTS = 23552   # dn_fps.hip: dn_fps_resident_max_points() (1024 threads x 23 points)
 FMAP_MAX_K = 64           # include/diffnet_hip.h: DN_FMAP_MAX_K
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # DN_LIB_VARIANT=<tag> selects libdiffnet_hip_<tag>.so (same sources, other build flags) for A/B experiments
@@ -115,6 +116,9 @@ _SIGNATURES = {
     "dn_knn_max_k": (C.c_int, []),
     "dn_knn_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "dn_knn_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "dn_fps_resident_max_points": (C.c_int, []),
+    "dn_fps_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dn_fps_f32": (C.c_int, [_vp, _vp] + [C.c_int] * 4 + [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "dn_cloud_operators_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [_vp] * 9),
     "dn_cloud_laplacian_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dn_cloud_star_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [_vp] * 4),

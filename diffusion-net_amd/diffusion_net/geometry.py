@@ -8,6 +8,8 @@ The host-side operator precompute keeps the reference's names here (``compute_op
 point-cloud operators: ``vertex_normals``, ``build_tangent_frames``, ``build_grad_point_cloud`` (the reference's names) and
 ``cloud_operators`` (normals, frames and gradient stencils of a cloud in one HIP pass over its neighbour table);
 ``point_cloud_laplacian`` is the local-Delaunay Laplacian and mass of a cloud (dn_cloud_lap.hip on the device).
+``farthest_point_sampling`` / ``farthest_point_samples`` thin a cloud (or a batch of clouds) with the sample loop on the device (dn_fps.hip);
+``norm`` .. ``face_normals`` are the reference's torch vector helpers.
 ``mesh_operators`` assembles what a triangle mesh needs in front of the eigenproblem -- frames, mass, cotan Laplacian, gradient operator
 -- on the device (dn_mesh.hip); ``compute_operators_via(..., assembly="device")`` builds the seven operators on it.
 ``geodesic_label_errors`` and ``get_all_pairs_geodesic_distance`` are the evaluation metric of the correspondence experiments: all-pairs
@@ -141,6 +143,129 @@ def find_knn(points_source, points_target, k, largest=False, omit_diagonal=False
     if method == "cpu_kd":
         return _knn_kdtree(points_source, points_target, k, omit_diagonal)
     return _knn_torch(points_source, points_target, k, largest, omit_diagonal)
+
+
+# ----------------------------------------------------------------------------------------------
+# torch vector helpers (geometry.py:24-90) and farthest point sampling (geometry.py:727-751)
+# ----------------------------------------------------------------------------------------------
+def norm(x, highdim=False):
+    """Length of every vector along the last dimension: (..., d) -> (...)."""
+    return torch.norm(x, dim=len(x.shape) - 1)
+
+
+def norm2(x, highdim=False):
+    """Squared length of every vector along the last dimension."""
+    return dot(x, x)
+
+
+def normalize(x, divide_eps=1e-6, highdim=False):
+    """Every vector divided by (its length + ``divide_eps``)."""
+    if len(x.shape) == 1:
+        raise ValueError("called normalize() on single vector of dim " + str(x.shape) + " are you sure?")
+    if not highdim and x.shape[-1] > 4:
+        raise ValueError("called normalize() with large last dimension " + str(x.shape) + " are you sure?")
+    return x / (norm(x, highdim=highdim) + divide_eps).unsqueeze(-1)
+
+
+def face_coords(verts, faces):
+    return verts[faces]
+
+
+def cross(vec_A, vec_B):
+    return torch.cross(vec_A, vec_B, dim=-1)
+
+
+def dot(vec_A, vec_B):
+    return torch.sum(vec_A * vec_B, dim=-1)
+
+
+def project_to_tangent(vecs, unit_normals):
+    """(..., 3) vectors with their component along the (unit) normals removed."""
+    dots = dot(vecs, unit_normals)
+    return vecs - unit_normals * dots.unsqueeze(-1)
+
+
+def _face_raw_normal(verts, faces):
+    coords = face_coords(verts, faces)
+    return cross(coords[:, 1, :] - coords[:, 0, :], coords[:, 2, :] - coords[:, 0, :])
+
+
+def face_area(verts, faces):
+    return 0.5 * norm(_face_raw_normal(verts, faces))
+
+
+def face_normals(verts, faces, normalized=True):
+    raw_normal = _face_raw_normal(verts, faces)
+    return normalize(raw_normal) if normalized else raw_normal
+
+
+def _fps_on_device(points):
+    """fp32 [V, 3] points on a ROCm device with nothing requiring grad: the HIP sampler (``ops.fps``, dn_fps.hip).  (Host tensors take this
+    route only while the tests have bound the emulator build of the same kernels.)"""
+    return ((points.is_cuda or ops._hip._allow_host_tensors) and points.dtype == torch.float32 and points.dim() == 2
+            and points.shape[1] == 3 and points.shape[0] > 0 and not points.requires_grad)
+
+
+def _fps_torch(points, n_sample):
+    """The reference's loop.  On a device the index stays a tensor: no host round trip per sample."""
+    N = points.shape[0]
+    chosen_mask = torch.zeros(N, dtype=torch.bool, device=points.device)
+    min_dists = torch.ones(N, dtype=points.dtype, device=points.device) * float("inf")
+    points = normalize_positions(points)
+    i = torch.min(norm2(points), dim=0).indices
+    chosen_mask[i] = True
+    for _ in range(n_sample - 1):
+        dists = norm2(points[i, :].unsqueeze(0) - points)
+        min_dists = torch.minimum(dists, min_dists)
+        i = torch.max(min_dists, dim=0).indices
+        if not points.is_cuda:
+            i = i.item()
+        chosen_mask[i] = True
+    return chosen_mask
+
+
+def farthest_point_sampling(points, n_sample):
+    """A [V] bool mask with ``n_sample`` points set (geometry.py:727-751): the point nearest the centre of the normalised cloud first, then
+    always the point farthest from those chosen so far; equal distances go to the lowest index.  ``n_sample == 0`` still sets the first
+    point, and with more samples than distinct points the lowest index is chosen again, so fewer than ``n_sample`` may be set -- both as
+    in the reference.
+
+    fp32 [V, 3] points on a ROCm device with nothing requiring grad are normalised with torch on the device and sampled by ``ops.fps``
+    (one launch for clouds up to ``ops._hip.FPS_RESIDENT_MAX_POINTS`` points, one per sample above); nothing synchronises with the host, so
+    the call can be captured in a graph.  Other device tensors run the reference's loop with the index kept on the device; host tensors do
+    what the reference does."""
+    N = points.shape[0]
+    if n_sample > N:
+        raise ValueError("not enough points to sample")
+    if not _fps_on_device(points):
+        return _fps_torch(points, n_sample)
+    pts = normalize_positions(points)
+    if torch.compiler.is_compiling():
+        from . import torchlib  # noqa: F401  (registers torch.ops.diffusion_net.fps)
+        order = torch.ops.diffusion_net.fps(pts, max(int(n_sample), 1))[0]
+    else:
+        order = ops.fps(pts, max(int(n_sample), 1))[0][0]
+    return torch.zeros(N, dtype=torch.bool, device=points.device).index_fill_(0, order, True)
+
+
+def farthest_point_samples(points_list, n_sample):
+    """``farthest_point_sampling`` of several clouds: the list of their masks.  Clouds the kernel takes (see there), all on one device, are
+    normalised one by one, packed back to back and sampled by ONE ``ops.fps`` call; anything else is sampled cloud by cloud."""
+    points_list = list(points_list)
+    for p in points_list:
+        if n_sample > p.shape[0]:
+            raise ValueError("not enough points to sample")
+    if (len(points_list) < 2 or not all(_fps_on_device(p) for p in points_list)
+            or any(p.device != points_list[0].device for p in points_list)):
+        return [farthest_point_sampling(p, n_sample) for p in points_list]
+    sizes = [p.shape[0] for p in points_list]
+    offsets = [0]
+    for n in sizes:
+        offsets.append(offsets[-1] + n)
+    packed = torch.cat([normalize_positions(p) for p in points_list])
+    order = ops.fps(packed, max(int(n_sample), 1), offsets=offsets)[0]
+    mask = torch.zeros(packed.shape[0], dtype=torch.bool, device=packed.device).index_fill_(0, order.reshape(-1), True)
+    return list(mask.split(sizes))
 
 
 # ----------------------------------------------------------------------------------------------

@@ -258,6 +258,87 @@ def knn(src, tgt, k, largest=False, omit_diagonal=False, n_split=0):
 
 
 @_on_device
+def _fps_launch(points, offsets, n_clouds, min_points, max_points, n_sample, start, route, return_min_dist):
+    L = _hip.lib()
+    dev = points.device
+    order = torch.empty(n_clouds, n_sample, dtype=torch.int64, device=dev)
+    radii = torch.empty(n_clouds, n_sample, dtype=torch.float32, device=dev)
+    md = torch.empty(points.shape[0], dtype=torch.float32, device=dev) if return_min_dist else None
+    nbytes = L.dn_fps_workspace_bytes(points.shape[0], n_clouds, max_points, n_sample, route)
+    ws = _hip.workspace(dev, nbytes) if nbytes else None
+    _hip.check(L.dn_fps_f32(points.data_ptr(), offsets.data_ptr(), n_clouds, min_points, max_points, n_sample, _hip.ptr(start), route,
+                            order.data_ptr(), radii.data_ptr(), _hip.ptr(md), _hip.ptr(ws), ws.numel() if ws is not None else 0,
+                            _hip.stream_of(points)), "dn_fps_f32")
+    return order, radii, md
+
+
+_fps_offset_cache = {}
+
+
+def _fps_offsets(sizes, device):
+    """The device copy of a batch's offsets.  One cloud: made by device kernels alone, so a call can be captured in a graph without a
+    warm-up; a batch: copied from the host once per (sizes, device) and kept (a capture after a warm-up call finds it here)."""
+    if len(sizes) == 1:
+        return torch.arange(2, dtype=torch.int64, device=device) * sizes[0]
+    key = (sizes, str(device))
+    offs = _fps_offset_cache.get(key)
+    if offs is None:
+        acc = [0]
+        for n in sizes:
+            acc.append(acc[-1] + n)
+        if len(_fps_offset_cache) >= 64:
+            _fps_offset_cache.clear()
+        offs = _fps_offset_cache[key] = torch.tensor(acc, dtype=torch.int64).to(device)
+    return offs
+
+
+def fps(points, n_sample, offsets=None, start=None, route=0, return_min_dist=False):
+    """Farthest point sampling of ``points`` [V, 3] fp32, ALREADY normalised (geometry.py:727-751), forward only -> (order [n_clouds,
+    n_sample] int64, radii [n_clouds, n_sample] fp32) and, with ``return_min_dist``, min_dist2 [V] fp32.  ``offsets`` (a list of Python ints
+    or an int64 HOST tensor, n_clouds + 1 entries, 0 first and V last; None: one cloud) packs several clouds back to back; ``order`` holds
+    rows of the packed array in the order chosen, ``radii`` the squared distance of each sample to the earlier ones when it was chosen (+inf
+    first).  ``start`` [n_clouds] int64 on the points' device names the first samples (None: the point nearest the origin).  ``route``: 0 the
+    library's choice, 1 the one-launch resident kernel (clouds up to ``_hip.FPS_RESIDENT_MAX_POINTS``), 2 one launch per sample; the
+    result does not depend on it.  Equal distances go to the lowest index."""
+    _hip.require_device(points)
+    points = _f32c(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("fps takes [V, 3] points (got %s)" % (tuple(points.shape),))
+    n_sample, route = int(n_sample), int(route)
+    if route not in (0, 1, 2):
+        raise ValueError("fps route must be 0 (library's choice), 1 (resident) or 2 (stepped)")
+    V = points.shape[0]
+    if offsets is None:
+        sizes_list = [V]
+    else:
+        if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+            raise ValueError("fps takes its offsets as host values (the cloud sizes select the kernel)")
+        off_list = [int(v) for v in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+        if len(off_list) < 1 or off_list[0] != 0 or off_list[-1] != V or any(b < a for a, b in zip(off_list, off_list[1:])):
+            raise ValueError("fps offsets must rise from 0 to the number of points")
+        sizes_list = [b - a for a, b in zip(off_list, off_list[1:])]
+    n_clouds = len(sizes_list)
+    if n_sample < 1:
+        raise ValueError("fps takes n_sample >= 1 (got %d)" % n_sample)
+    if n_clouds == 0:
+        empty = (torch.empty(0, n_sample, dtype=torch.int64, device=points.device), torch.empty(0, n_sample, dtype=torch.float32, device=points.device))
+        return empty + (torch.empty(0, dtype=torch.float32, device=points.device),) if return_min_dist else empty
+    min_points, max_points = min(sizes_list), max(sizes_list)
+    if n_sample > min_points:
+        raise ValueError("not enough points to sample")
+    if route == 1 and max_points > _hip.FPS_RESIDENT_MAX_POINTS:
+        raise ValueError("fps resident route takes clouds of at most %d points (got %d)" % (_hip.FPS_RESIDENT_MAX_POINTS, max_points))
+    offs = _fps_offsets(tuple(sizes_list), points.device)
+    if start is not None:
+        _hip.require_device(start)
+        if start.dtype != torch.int64 or tuple(start.shape) != (n_clouds,) or start.device != points.device:
+            raise ValueError("fps start must be [n_clouds] int64 on the points' device")
+        start = start.contiguous()
+    order, radii, md = _fps_launch(points, offs, n_clouds, min_points, max_points, n_sample, start, route, bool(return_min_dist))
+    return (order, radii, md) if return_min_dist else (order, radii)
+
+
+@_on_device
 def _cloud_launch(points, nbr, normals_in):
     n, k = nbr.shape
     dev = points.device

@@ -299,6 +299,18 @@ def _(src, tgt, k, largest, omit_diagonal):
     return src.new_empty(src.shape[0], k, dtype=torch.float32), src.new_empty(src.shape[0], k, dtype=torch.int64)   # ops.knn is fp32
 
 
+# ------------------------------------------------------------------------------------------------ farthest point sampling (forward only)
+@_op("diffusion_net::fps")
+def fps(points: Tensor, n_sample: int) -> Tuple[Tensor, Tensor]:
+    order, radii = ops.fps(points, n_sample)
+    return order[0], radii[0]
+
+
+@fps.register_fake
+def _(points, n_sample):
+    return points.new_empty(n_sample, dtype=torch.int64), points.new_empty(n_sample, dtype=torch.float32)   # ops.fps is fp32
+
+
 # ------------------------------------------------------------------------------------------------ point-cloud Laplacian (forward only)
 @_op("diffusion_net::cloud_laplacian")
 def cloud_laplacian(points: Tensor, nbr: Tensor, frames: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:

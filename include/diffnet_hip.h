@@ -339,6 +339,30 @@ size_t dn_knn_workspace_bytes(int n_src, int n_tgt, int dim, int k, int n_split)
 int dn_knn_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int largest, int omit_diagonal, int n_split,
                float* dist, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- geometry.farthest_point_sampling (geometry.py:727-751): farthest point sampling with the sample loop on the device (dn_fps.hip).
+ *      pts [V, 3] fp32 row-major, already normalised: one cloud, or n_clouds clouds packed back to back with offsets [n_clouds + 1] int64
+ *      ON THE DEVICE (cloud c is rows offsets[c] .. offsets[c+1] - 1).  order [n_clouds, n_sample] int64: rows of the packed array in the
+ *      order chosen; radii [n_clouds, n_sample] fp32: the squared distance of each sample to the nearest earlier one at the moment it was
+ *      chosen (+inf for the first; it never increases); min_dist2 [V] fp32 or NULL: the squared distance of every point to the nearest of
+ *      the n_sample samples.  start [n_clouds] int64 on the device (rows of the packed array, clamped into their cloud) names the first
+ *      sample of every cloud; NULL: the point of smallest |p|^2, the lowest index among equals.
+ *      Squared distances are (dx*dx + dy*dy) + dz*dz in fp32 with every product and sum rounded on its own (no FMA); the next sample is the
+ *      point of largest min_d, the lowest index among equals.  The result is bit-identical from run to run and for both routes.  Once
+ *      every min_d is 0 (more samples than distinct points) the lowest index of the cloud is chosen again.  Inputs are assumed finite;
+ *      non-finite coordinates cannot cause an out-of-range access (no address depends on a point's value).
+ *      route: 0 = the library chooses (resident when max_points <= dn_fps_resident_max_points(), else stepped), 1 = resident (one
+ *      workgroup per cloud, one launch), 2 = stepped (one launch per sample + 1, many workgroups per cloud; needs the workspace).
+ *      min_points / max_points: the sizes of the smallest and the largest cloud (host values: the call never reads device memory).
+ *      dn_fps_workspace_bytes: 0 for the resident route; for the stepped route it depends on n_clouds and max_points only (min_d is kept
+ *      at a per-cloud stride the call can check; n_points_total <= 0 answers 0).
+ *      Returns 0 on success (n_clouds == 0: nothing is launched) and non-zero WITHOUT launching for n_sample < 1, n_sample > min_points,
+ *      max_points < min_points, route == 1 with max_points beyond the capacity, an unknown route, n_clouds < 0 (stepped: > 65535), or a
+ *      workspace smaller than the query says. */
+int dn_fps_resident_max_points(void);
+size_t dn_fps_workspace_bytes(int64_t n_points_total, int n_clouds, int max_points, int n_sample, int route);
+int dn_fps_f32(const float* pts, const int64_t* offsets, int n_clouds, int min_points, int max_points, int n_sample, const int64_t* start,
+               int route, int64_t* order, float* radii, float* min_dist2, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- point-cloud frames and gradient stencils (geometry.py:92-99, 114-123, 151-206, 209-273 for a cloud): what the reference computes
  *      per point from the indices of its k nearest neighbours, in one pass (dn_cloud.hip).  pts [n,3] fp32; nbr [n,k] int64 as dn_knn_f32
  *      writes them (omit_diagonal).  With e_j = pts[nbr[i,j]] - pts[i] (centred on the point, not on the neighbourhood mean):
