@@ -137,6 +137,12 @@ _SIGNATURES = {
     "dn_minplus_sweeps_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     "dn_cheb_rows_per_workgroup": (C.c_int, []),
     "dn_cheb_step_f64": (C.c_int, [_vp] * 3 + [C.c_int] + [_vp] * 3 + [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _vp]),
+    "dn_implicit_rows_per_tile": (C.c_int, []),
+    "dn_implicit_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "dn_implicit_init_f32": (C.c_int, [_vp] * 6 + [C.c_int, _vp] + [C.c_int] * 3 + [_vp, C.c_int, _vp, C.c_double, _vp, C.c_size_t, _vp]),
+    "dn_implicit_iterate_f32": (C.c_int, [_vp] * 6 + [C.c_int, _vp] + [C.c_int] * 4 + [_vp, _vp, C.c_size_t, _vp]),
+    "dn_implicit_finish_f32": (C.c_int, [_vp, _vp, C.c_int, _vp] + [C.c_int] * 4 + [_vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "dn_implicit_lx_dot_f32": (C.c_int, [_vp] * 4 + [C.c_int, _vp] + [C.c_int] * 3 + [_vp, _vp, _vp, C.c_size_t, _vp]),
     "dn_coo_to_csr_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "dn_coo_to_csr_i64": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int] + [_vp] * 7 + [_vp, C.c_size_t, _vp]),
     "dn_checksum128": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp, _vp]),

@@ -367,12 +367,16 @@ def _shared_pattern(gx: torch.Tensor, gy: torch.Tensor):
         zy = torch.sparse_coo_tensor(ix, torch.zeros_like(gx.values()), gx.shape)
         ux, uy = (gx + zx).coalesce(), (gy + zy).coalesce()
         idx, vx, vy = ux.indices(), ux.values(), uy.values()
-    if idx.shape[0] == 3:
-        V = gx.shape[-1]
-        rows, cols = idx[0] * V + idx[1], idx[0] * V + idx[2]
-    else:
-        rows, cols = idx[0], idx[1]
+    rows, cols = global_coo(idx, gx.shape[-1])
     return rows, cols, vx, vy
+
+
+def global_coo(idx: torch.Tensor, V: int):
+    """(rows, cols) on the concatenated vertex axis from the indices of a coalesced sparse [V, V] (2 x nnz) or batched [B, V, V] (3 x nnz)
+    tensor: mesh b's vertex i is row b * V + i.  Row-sorted, because coalesced indices are."""
+    if idx.shape[0] == 3:
+        return idx[0] * V + idx[1], idx[0] * V + idx[2]
+    return idx[0], idx[1]
 
 
 class GatherPattern:

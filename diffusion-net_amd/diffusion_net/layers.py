@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip, autograph, ops
-from .batch import GatherPattern, MeshBatch, operator_cache
+from .batch import GatherPattern, MeshBatch, coo_to_csr, global_coo, operator_cache
 
 _MIN_TIME = 1e-8
 
@@ -74,14 +74,39 @@ def _batch_of(mass, evals, evecs, gradX=None, gradY=None):
                                  lambda: (MeshBatch.from_reference_args(mass, evals, evecs, gradX, gradY), None))[0]
 
 
+def _implicit_operator_of(L, mass):
+    """The packed operator of ``method='implicit_sparse'`` from reference-style operands (L torch sparse [V, V] or [B, V, V], mass [V] or
+    [B, V]): L as int32 CSR over the concatenated vertex axis with fp32 values (``batch.coo_to_csr``, the values in the vx slot), packed once
+    per distinct operator (``operator_cache``, as gradX / gradY are)."""
+    if L is None or not L.is_sparse:
+        raise ValueError("diffusion_method='implicit_sparse' takes L as a torch sparse tensor [V, V] or [B, V, V]")
+    if L.requires_grad or mass.requires_grad:
+        raise RuntimeError("diffusion_method='implicit_sparse' has no gradient for mass or L")
+
+    def pack():
+        Lc = L if L.is_coalesced() else L.coalesce()          # row-sorted, duplicates summed
+        V = int(L.shape[-1])
+        B = int(L.shape[0]) if L.dim() == 3 else 1
+        rows, cols = global_coo(Lc.indices(), V)
+        if mass.numel() != B * V:
+            raise ValueError("mass %s does not match L %s" % (tuple(mass.shape), tuple(L.shape)))
+        rowptr, col, val = coo_to_csr(rows, 1, cols, Lc.values(), None, B * V, B * V)[:3]
+        return ops.ImplicitOperator(rowptr, col, val, mass.detach().to(torch.float32).reshape(-1).contiguous(), [V] * B, validate=False), None
+    return operator_cache.lookup(mass, None, None, L, None, None, ("implicit",), pack)[0]
+
+
 class LearnedTimeDiffusion(nn.Module):
-    """Per-channel learned-time heat diffusion (reference layers.py:17-90)."""
+    """Per-channel learned-time heat diffusion (reference layers.py:17-90).  ``method``: 'spectral', 'implicit_dense' (the reference's dense
+    Cholesky solve, toy sizes) or 'implicit_sparse': the same backward-Euler step (M + t_c L) x_c = M u_c solved per channel by sparse
+    conjugate gradients on the device (``ops.ImplicitDiffusionFn``, dn_implicit.hip; evals / evecs are not used and may be None).  Its solver
+    settings are plain attributes, not parameters: the state dict is the same for every method."""
 
     def __init__(self, C_inout, method="spectral"):
         super().__init__()
         self.C_inout = C_inout
         self.diffusion_time = nn.Parameter(torch.zeros(C_inout))      # layers.py:38,41
         self.method = method
+        self.implicit_rtol, self.implicit_max_iter, self.implicit_check = 1e-9, 1000, True
 
     def clamp_time_(self):
         # same observable side effect as layers.py:48-49 (the Parameter holds its clamp afterwards, so the
@@ -102,6 +127,11 @@ class LearnedTimeDiffusion(nn.Module):
         if self.method == "spectral":
             mb = _batch_of(mass, evals, evecs)
             out = ops.DiffusionFn.apply(x.reshape(-1, self.C_inout), self.diffusion_time, mb)
+            return out.reshape(x.shape)
+        if self.method == "implicit_sparse":
+            op = _implicit_operator_of(L, mass)
+            out = ops.ImplicitDiffusionFn.apply(x.reshape(-1, self.C_inout), self.diffusion_time, op, self.implicit_rtol, self.implicit_max_iter,
+                                                self.implicit_check)
             return out.reshape(x.shape)
         if self.method == "implicit_dense":
             # Toy-size dense solve (reference layers.py:69-84); not part of the accelerated path
@@ -253,7 +283,7 @@ class DiffusionNetBlock(nn.Module):
         return self.forward_packed(x_in.reshape(-1, self.C_width), mb).reshape(x_in.shape)
 
     def _forward_unfused(self, x_in, mass, L, evals, evecs, gradX, gradY):
-        # only reached for diffusion_method='implicit_dense' (toy sizes, out of the accelerated scope)
+        # diffusion_method='implicit_sparse' (the diffusion on its own kernels, the rest through the unfused ops) and 'implicit_dense' (toy sizes)
         xd = self.diffusion(x_in, L, mass, evals, evecs)
         feats = [x_in, xd]
         if self.with_gradient_features:
@@ -282,7 +312,7 @@ class DiffusionNet(nn.Module):
         self.mlp_hidden_dims = mlp_hidden_dims
         self.dropout = dropout
         self.diffusion_method = diffusion_method
-        if diffusion_method not in ["spectral", "implicit_dense"]:
+        if diffusion_method not in ["spectral", "implicit_dense", "implicit_sparse"]:
             raise ValueError("invalid setting for diffusion_method")
         self.with_gradient_features = with_gradient_features
         self.with_gradient_rotations = with_gradient_rotations
@@ -388,6 +418,8 @@ class DiffusionNet(nn.Module):
 
         if self.diffusion_method != "spectral":
             mass_b, L_b, evals_b, evecs_b, gX_b, gY_b, edges_b, faces_b = batched()
+            if self.diffusion_method == "implicit_sparse":
+                L_b = L       # as handed over ([V, V] is one mesh): its packed operator is keyed on the caller's tensor, not on a copy made here
             return self._forward_unfused(x_in.unsqueeze(0) if squeeze else x_in, mass_b, L_b, evals_b, evecs_b, gX_b, gY_b, edges_b, faces_b, squeeze)
 
         if squeeze:
@@ -422,7 +454,7 @@ class DiffusionNet(nn.Module):
         return out.squeeze(0) if squeeze else out
 
     def _forward_unfused(self, x_in, mass, L, evals, evecs, gradX, gradY, edges, faces, squeeze):
-        # diffusion_method='implicit_dense' only (outside the accelerated scope; see LearnedTimeDiffusion)
+        # diffusion_method='implicit_sparse' and 'implicit_dense' (see LearnedTimeDiffusion); eager, no graph replay
         x = self.first_lin(x_in)
         for blk in self.blocks:
             x = blk(x, mass, L, evals, evecs, gradX, gradY)

@@ -759,6 +759,209 @@ def cheb_step(rowptr, col, val, Y, Z, alpha, beta, gamma, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# implicit diffusion: (diag(m) + t_c L) x_c = m u_c per mesh and channel by Jacobi-preconditioned conjugate gradients
+# (include/diffnet_hip.h: dn_implicit_*_f32; the recurrence in numpy: precompute.implicit_diffusion_host)
+# ----------------------------------------------------------------------------------------------
+_implicit_tables = {}
+_implicit_checked = []        # [(weakref rowptr, weakref col, their versions)]: the CSR patterns validated last, newest first
+
+
+def _implicit_check_pattern(rowptr, col, n_rows):
+    """Row pointer and column range of a CSR pattern, read back from the device ONCE per pattern (as ``_cheb_check_pattern``); the last eight
+    patterns are remembered, by the identity and version of their tensors."""
+    stamp = (rowptr._version, col._version, n_rows)
+    for seen in _implicit_checked:
+        if seen[0]() is rowptr and seen[1]() is col and seen[2] == stamp:
+            return
+    nnz = col.numel()
+    rp = rowptr.to(torch.int64)
+    if int(rp[0]) != 0 or int(rp[-1]) != nnz or (n_rows and bool((rp[1:] < rp[:-1]).any())):
+        raise ValueError("implicit_solve: rowptr is not a non-decreasing row pointer of %d entries" % nnz)
+    if nnz and (int(col.min()) < 0 or int(col.max()) >= n_rows):
+        raise ValueError("implicit_solve: a column index is outside [0, %d)" % n_rows)
+    _implicit_checked.insert(0, (weakref.ref(rowptr), weakref.ref(col), stamp))
+    del _implicit_checked[8:]
+
+
+def _implicit_tables_on(device, sizes):
+    """(tiles [n_tiles, 4] int32, mesh_tile_off [n_mesh + 1] int32) on ``device``: runs of at most ``dn_implicit_rows_per_tile()`` rows that
+    never straddle two meshes, built from the mesh sizes once per (device, sizes)."""
+    import numpy as np
+    R = int(_hip.lib().dn_implicit_rows_per_tile())
+    key = (str(device), tuple(sizes), R)
+    hit = _implicit_tables.get(key)
+    if hit is None:
+        if len(_implicit_tables) > 256:
+            _implicit_tables.clear()
+        tiles, off, row0 = [], [0], 0
+        for m, v in enumerate(sizes):
+            tiles += [(row0 + r, min(R, v - r), m, 0) for r in range(0, v, R)]
+            off.append(len(tiles))
+            row0 += v
+        hit = (torch.from_numpy(np.array(tiles, dtype=np.int32).reshape(-1, 4)).to(device), torch.from_numpy(np.array(off, dtype=np.int32)).to(device))
+        _implicit_tables[key] = hit
+    return hit
+
+
+class ImplicitOperator:
+    """The operands of the implicit diffusion that do not change from call to call: L in CSR (int32 ``rowptr`` [V + 1] and ``col`` [nnz], fp32
+    ``val`` [nnz], block diagonal over the meshes), ``mass`` [V] fp32, the rows of every mesh (``sizes``, default one mesh) and the tile
+    tables made from them.  ``validate=False``: the pattern comes from ``batch.coo_to_csr``, which has checked it."""
+
+    def __init__(self, rowptr, col, val, mass, sizes=None, *, validate=True):
+        for t in (rowptr, col, val, mass):
+            _hip.require_device(t)
+        if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or val.dtype != torch.float32 or mass.dtype != torch.float32:
+            raise TypeError("implicit_solve takes int32 rowptr and col and fp32 values and mass (got %s, %s, %s, %s)"
+                            % (rowptr.dtype, col.dtype, val.dtype, mass.dtype))
+        if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1 or val.dim() != 1 or col.numel() != val.numel() or mass.dim() != 1:
+            raise ValueError("implicit_solve takes CSR arrays rowptr [V + 1], col [nnz], val [nnz] and mass [V]")
+        V = rowptr.numel() - 1
+        if mass.numel() != V:
+            raise ValueError("implicit_solve: mass has %d entries for %d rows" % (mass.numel(), V))
+        if not (rowptr.device == col.device == val.device == mass.device):
+            raise RuntimeError("implicit_solve: the operands are on %s, %s, %s and %s" % (rowptr.device, col.device, val.device, mass.device))
+        if mass.requires_grad or val.requires_grad:
+            raise RuntimeError("implicit_solve has no gradient for mass or L")
+        self.sizes = [V] if sizes is None else [int(s) for s in sizes]
+        if sum(self.sizes) != V or any(s < 1 for s in self.sizes):
+            raise ValueError("implicit_solve: sizes %s are not positive row counts that sum to %d" % (self.sizes if len(self.sizes) < 9 else "[...]", V))
+        self.rowptr, self.col, self.val, self.mass = rowptr.contiguous(), col.contiguous(), val.contiguous(), mass.contiguous()
+        self.V, self.device = V, mass.device
+        if validate and V:
+            _implicit_check_pattern(self.rowptr, self.col, V)
+        self.tiles, self.mesh_tile_off = _implicit_tables_on(self.device, self.sizes) if V else (None, None)
+        self.n_tiles = int(self.tiles.shape[0]) if V else 0
+
+    @property
+    def n_mesh(self):
+        return len(self.sizes)
+
+
+def _implicit_block(name, t, op, C=None):
+    _hip.require_device(t)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != op.V or (C is not None and t.shape[1] != C):
+        raise TypeError("implicit_solve: %s must be an fp32 block [%d, %s] (got %s %s)" % (name, op.V, "C" if C is None else C, t.dtype, tuple(t.shape)))
+    if t.device != op.device:
+        raise RuntimeError("implicit_solve: %s is on %s, the operator on %s" % (name, t.device, op.device))
+    return t.contiguous()
+
+
+@_on_device
+def _implicit_run(rhs, time, x0, lx_x, op, rhs_mass, rtol, max_iter, iters_per_check, check):
+    """One solve on a packed operator.  ``rhs_mass``: the right side is m (.) rhs and the result x (forward); else the right side is rhs and
+    the result m (.) x (backward: d_u), and with ``lx_x`` (the forward's x) the gradient of the times is returned too.
+    -> (out [V, C] fp32, info, d_time [C] fp32 or None)."""
+    L, dev = _hip.lib(), op.device
+    V, Cc, nm = op.V, rhs.shape[1], op.n_mesh
+    out = torch.empty_like(rhs)
+    iters = torch.zeros(nm, Cc, dtype=torch.int32, device=dev)
+    res = torch.zeros(nm, Cc, dtype=torch.float64, device=dev)
+    info = {"iterations": iters, "residual": res, "launches": 0}
+    d_time = torch.zeros(Cc, dtype=torch.float32, device=dev) if lx_x is not None else None
+    if V == 0 or Cc == 0:
+        return out, info, d_time
+    ws = _hip.workspace(dev, max(int(L.dn_implicit_workspace_bytes(V, Cc, op.n_tiles, nm)), 1024))
+    st = _hip.stream_of(rhs)
+    table = (op.tiles.data_ptr(), op.n_tiles, op.mesh_tile_off.data_ptr(), nm, V, Cc)
+    csr = (op.rowptr.data_ptr(), _hip.ptr(op.col) if op.col.numel() else None, _hip.ptr(op.val) if op.val.numel() else None)
+    if op.col.numel() == 0:                      # L = 0 (every row empty): the library takes non-NULL arrays
+        pad = torch.zeros(1, dtype=torch.int32, device=dev)
+        csr = (csr[0], pad.data_ptr(), pad.data_ptr())
+    _hip.check(L.dn_implicit_init_f32(*csr, op.mass.data_ptr(), time.data_ptr(), *table, rhs.data_ptr(), 1 if rhs_mass else 0, _hip.ptr(x0),
+                                      float(rtol), ws.data_ptr(), ws.numel(), st), "dn_implicit_init_f32")
+    info["launches"] += 2
+    unfinished = torch.empty(1, dtype=torch.int32, device=dev)
+    done = 0
+    while True:
+        n = max(0, min(iters_per_check if check else max_iter, max_iter - done))
+        _hip.check(L.dn_implicit_iterate_f32(*csr, op.mass.data_ptr(), time.data_ptr(), *table, n, unfinished.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             st), "dn_implicit_iterate_f32")
+        done += n
+        info["launches"] += 4 * n + 1
+        if not check:
+            break
+        left = int(unfinished.item())            # the one host read per group of iterations
+        if left == 0:
+            break
+        if done >= max_iter:
+            raise RuntimeError("implicit_solve: %d iterations did not reach rtol = %g (%d of %d systems left)" % (done, rtol, left, nm * Cc))
+    _hip.check(L.dn_implicit_finish_f32(op.mass.data_ptr(), *table, 0 if rhs_mass else 1, out.data_ptr(), iters.data_ptr(), res.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), st), "dn_implicit_finish_f32")
+    info["launches"] += 1
+    if lx_x is not None:
+        _hip.check(L.dn_implicit_lx_dot_f32(*csr, *table, lx_x.data_ptr(), d_time.data_ptr(), ws.data_ptr(), ws.numel(), st), "dn_implicit_lx_dot_f32")
+        info["launches"] += 2
+    return out, info, d_time
+
+
+def _implicit_settings(rtol, max_iter, iters_per_check):
+    rtol, max_iter, iters_per_check = float(rtol), int(max_iter), int(iters_per_check)
+    if not rtol >= 0.0:
+        raise ValueError("rtol must be >= 0")
+    if max_iter < 0 or iters_per_check < 1:
+        raise ValueError("max_iter must be >= 0 and iters_per_check >= 1")
+    return rtol, max_iter, iters_per_check
+
+
+def _implicit_time(time, op, Cc):
+    _hip.require_device(time)
+    if time.dtype != torch.float32 or time.dim() != 1 or time.numel() != Cc:
+        raise TypeError("implicit_solve: time must be fp32 [%d] (got %s %s)" % (Cc, time.dtype, tuple(time.shape)))
+    if time.device != op.device:
+        raise RuntimeError("implicit_solve: time is on %s, the operator on %s" % (time.device, op.device))
+    return time.contiguous()
+
+
+def implicit_solve(rowptr, col, val, mass, time, rhs, sizes=None, *, x0=None, rtol=1e-9, max_iter=1000, iters_per_check=16, check=True,
+                   return_info=False):
+    """Implicit (backward-Euler) diffusion, forward only (dn_implicit.hip): for every mesh b and channel c
+    ``x_bc = (diag(m_b) + time[c] L_b)^-1 (m_b * rhs_bc)`` by Jacobi-preconditioned conjugate gradients started at ``x0`` (default ``rhs``: for
+    small times no iteration is needed).  ``rowptr`` [V + 1], ``col`` [nnz] int32, ``val`` [nnz] fp32: L in CSR, block diagonal over the
+    meshes; ``mass`` [V], ``time`` [C] (positive: the caller clamps), ``rhs`` and ``x0`` [V, C] fp32; ``sizes``: the rows of every mesh
+    (default one mesh).  -> [V, C] fp32.  All solver state is fp64; a system is done when ||r|| <= ``rtol`` ||m * rhs|| over its mesh's
+    rows and is frozen from then on; norms and scalars are per (mesh, channel), sums have one fixed order: two calls give the same bits.
+
+    ``check=True``: the device's count of unfinished systems is read after every ``iters_per_check`` iterations (this form synchronises with
+    the host), the loop stops on 0 and ``RuntimeError`` ("did not reach rtol") is raised when ``max_iter`` iterations leave a system
+    unfinished.  ``check=False``: exactly ``max_iter`` iterations, no host read -- the capturable form; the caller reads ``info``.
+    ``return_info``: also a dict ``iterations`` [n_mesh, C] int32, ``residual`` [n_mesh, C] fp64 (the recurrence's final ||r|| / ||b||),
+    ``launches``.  ``ValueError`` before any launch for a rowptr or col out of range or sizes that do not sum to V; ``RuntimeError`` for
+    host tensors.  The pattern is validated on its first use, which reads the device (the last eight patterns are remembered by the identity
+    of their ``rowptr`` / ``col`` tensors): call once eagerly with the same tensors before capturing the check=False form in a graph."""
+    op = ImplicitOperator(rowptr, col, val, mass, sizes)
+    rhs = _implicit_block("rhs", rhs, op)
+    time = _implicit_time(time, op, rhs.shape[1])
+    if x0 is not None:
+        x0 = _implicit_block("x0", x0, op, rhs.shape[1])
+    rtol, max_iter, iters_per_check = _implicit_settings(rtol, max_iter, iters_per_check)
+    out, info, _ = _implicit_run(rhs.detach(), time.detach(), x0.detach() if x0 is not None else None, None, op, True, rtol, max_iter,
+                                 iters_per_check, bool(check))
+    return (out, info) if return_info else out
+
+
+class ImplicitDiffusionFn(torch.autograd.Function):
+    """x = (diag(m) + t_c L)^-1 (m u_c) on a packed ``ImplicitOperator`` with gradients for u and the times (A symmetric, g = A^-1 d_x by the
+    same solver started at d_x / m):  d_u = m g,  d_t[c] = - sum_b g_bc . (L_b x_bc), L x from an explicit product.  Saves the fp32 x."""
+
+    @staticmethod
+    def forward(ctx, u, time, operator, rtol=1e-9, max_iter=1000, check=True, iters_per_check=16):
+        u = _implicit_block("u", u, operator)
+        time = _implicit_time(time, operator, u.shape[1])
+        ctx.settings = _implicit_settings(rtol, max_iter, iters_per_check) + (bool(check),)
+        x, ctx.info, _ = _implicit_run(u, time, None, None, operator, True, *ctx.settings)
+        ctx.operator = operator
+        ctx.save_for_backward(x, time)
+        return x
+
+    @staticmethod
+    def backward(ctx, d_x):
+        x, time = ctx.saved_tensors
+        d_u, _, d_t = _implicit_run(_implicit_block("d_x", d_x, ctx.operator, x.shape[1]), time, None, x, ctx.operator, False, *ctx.settings)
+        return d_u, d_t, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------
 # functional maps: the regularised spectral solve (include/diffnet_hip.h: dn_fmap_solve_*_f32)
 # ----------------------------------------------------------------------------------------------
 def _fmap_ws(A):

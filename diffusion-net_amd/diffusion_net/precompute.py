@@ -334,6 +334,64 @@ def laplacian_eigenbasis_subspace(L, massvec, k_eig, *, rtol=1e-9, seed=0, max_i
     return (*out, info) if return_info else out
 
 
+def implicit_diffusion_host(L, mass, time, u, sizes=None, *, x0=None, rtol=1e-9, max_iter=1000, return_info=False):
+    """The recurrence of ``ops.implicit_solve`` (dn_implicit.hip) in numpy fp64, all channels at once: for every mesh b (``sizes``: its rows;
+    default one mesh) and channel c, ``(diag(m_b) + time[c] L_b) x = m_b * u`` by Jacobi-preconditioned conjugate gradients.
+
+        d = m + t diag(L);  x = x0 (default u);  r = m u - A x;  z = r / d;  p = z;  rz = r.z
+        until ||r|| <= rtol ||m u||:   q = A p;  alpha = rz / p.q;  x += alpha p;  r -= alpha q;  z = r / d;
+                                       rz' = r.z;  beta = rz' / rz;  p = z + beta p;  rz = rz'
+
+    Norms and dot products are per (mesh, channel), over that mesh's rows.  A system that is done is frozen (its x, r, p stop changing) and
+    the loop ends when every system is done; ``RuntimeError`` when ``max_iter`` iterations leave one unfinished.  The operands are taken as
+    they are (fp32 arrays are widened).  -> x [V, C] fp64, with ``return_info`` also {"iterations" [n_mesh, C], "residual" [n_mesh, C]}."""
+    L = sp.csr_matrix(L).astype(np.float64)
+    m = np.asarray(mass, dtype=np.float64).reshape(-1)
+    t = np.asarray(time, dtype=np.float64).reshape(-1)
+    u = np.asarray(u, dtype=np.float64)
+    V, C = u.shape
+    sizes = [V] if sizes is None else [int(s) for s in sizes]
+    if sum(sizes) != V or L.shape != (V, V) or m.shape != (V,) or t.shape != (C,):
+        raise ValueError("implicit_diffusion_host takes L [V, V], mass [V], time [C], u [V, C] and sizes that sum to V")
+    seg = np.concatenate([[0], np.cumsum(sizes)])[:-1]
+    mesh_of = np.repeat(np.arange(len(sizes)), sizes)
+    dots = lambda a, b: np.add.reduceat(a * b, seg, axis=0) if V else np.zeros((len(sizes), C))      # [n_mesh, C]
+    A = lambda y: m[:, None] * y + t[None, :] * (L @ y)
+    d = m[:, None] + t[None, :] * L.diagonal()[:, None]
+    b = m[:, None] * u
+    x = u.copy() if x0 is None else np.array(x0, dtype=np.float64)
+    r = b - A(x)
+    p = r / d
+    rz, rr, thr = dots(r, p), dots(r, r), rtol * np.sqrt(dots(b, b))
+    done = np.sqrt(rr) <= thr
+    iters = np.zeros(done.shape, dtype=np.int64)
+    it = 0
+    while not done.all():
+        if it >= max_iter:
+            raise RuntimeError("implicit diffusion (host): %d iterations did not reach rtol = %g (%d systems left)" % (it, rtol, int((~done).sum())))
+        live = ~done                                             # [n_mesh, C]: the systems this iteration advances
+        rows = live[mesh_of]                                     # [V, C]
+        q = A(p)
+        with np.errstate(all="ignore"):
+            alpha = np.where(live, rz / dots(p, q), 0.0)
+            x = np.where(rows, x + alpha[mesh_of] * p, x)
+            r = np.where(rows, r - alpha[mesh_of] * q, r)
+            z = r / d
+            rz_new = dots(r, z)
+            beta = np.where(live, rz_new / rz, 0.0)
+        rz, rr = np.where(live, rz_new, rz), np.where(live, dots(r, r), rr)
+        iters += live
+        done = done | (live & (np.sqrt(rr) <= thr))
+        with np.errstate(all="ignore"):
+            p = np.where((~done)[mesh_of], z + beta[mesh_of] * p, p)
+        it += 1
+    if return_info:
+        with np.errstate(all="ignore"):
+            res = np.where(rr == 0.0, 0.0, np.sqrt(rr) / np.sqrt(dots(b, b)))
+        return x, {"iterations": iters, "residual": res}
+    return x
+
+
 EIGENSOLVERS = (None, "subspace")
 
 

@@ -394,3 +394,53 @@ def cheb_step(rowptr: Tensor, col: Tensor, val: Tensor, Y: Tensor, Z: Optional[T
 @cheb_step.register_fake
 def _(rowptr, col, val, Y, Z, alpha, beta, gamma):
     return Y.new_empty(Y.shape, dtype=torch.float64)
+
+
+# ------------------------------------------------------------------------------------------------ implicit diffusion (sparse per-channel PCG)
+def _implicit_op(rowptr, col, val, mass, sizes):
+    return ops.ImplicitOperator(rowptr, col, val, mass, list(sizes) if sizes else None)
+
+
+@_op("diffusion_net::implicit_solve")
+def implicit_solve(rowptr: Tensor, col: Tensor, val: Tensor, mass: Tensor, time: Tensor, rhs: Tensor, sizes: List[int], x0: Optional[Tensor],
+                   rtol: float, max_iter: int) -> Tensor:
+    """``ops.implicit_solve(..., check=False)``: exactly ``max_iter`` iterations, no host read (``sizes`` empty: one mesh) -- once the pattern
+    has been validated: the first call with given ``rowptr`` / ``col`` tensors reads their range back, so make it outside a graph capture."""
+    return ops.implicit_solve(rowptr, col, val, mass, time, rhs, list(sizes) if sizes else None, x0=x0, rtol=rtol, max_iter=max_iter, check=False)
+
+
+@implicit_solve.register_fake
+def _(rowptr, col, val, mass, time, rhs, sizes, x0, rtol, max_iter):
+    return rhs.new_empty(rhs.shape, dtype=torch.float32)
+
+
+@_op("diffusion_net::implicit_solve_bwd")
+def implicit_solve_bwd(d_x: Tensor, x: Tensor, rowptr: Tensor, col: Tensor, val: Tensor, mass: Tensor, time: Tensor, sizes: List[int], rtol: float,
+                       max_iter: int) -> Tuple[Tensor, Tensor]:
+    """-> (d_rhs, d_time): g = A^-1 d_x by the same solver, d_rhs = m g, d_time[c] = - sum_b g_bc . (L_b x_bc)."""
+    op = _implicit_op(rowptr, col, val, mass, sizes)
+    d_u, _, d_t = ops._implicit_run(ops._implicit_block("d_x", d_x, op, x.shape[1]), ops._implicit_time(time, op, x.shape[1]), None,
+                                    ops._implicit_block("x", x, op), op, False, *ops._implicit_settings(rtol, max_iter, 16), False)
+    return d_u, d_t
+
+
+@implicit_solve_bwd.register_fake
+def _(d_x, x, rowptr, col, val, mass, time, sizes, rtol, max_iter):
+    return torch.empty_like(x), time.new_empty(time.shape, dtype=torch.float32)
+
+
+def _implicit_setup(ctx, inputs, output):
+    rowptr, col, val, mass, time, rhs, sizes, x0, rtol, max_iter = inputs
+    if mass.requires_grad or val.requires_grad:
+        raise RuntimeError("implicit_solve has no gradient for mass or L")
+    ctx.sizes, ctx.rtol, ctx.max_iter = sizes, rtol, max_iter
+    ctx.save_for_backward(output, rowptr, col, val, mass, time)
+
+
+def _implicit_backward(ctx, g):
+    x, rowptr, col, val, mass, time = ctx.saved_tensors
+    d_u, d_t = implicit_solve_bwd(g.contiguous(), x, rowptr, col, val, mass, time, ctx.sizes, ctx.rtol, ctx.max_iter)
+    return None, None, None, None, d_t, d_u, None, None, None, None        # (x0 is only where the iteration starts)
+
+
+implicit_solve.register_autograd(_implicit_backward, setup_context=_implicit_setup)

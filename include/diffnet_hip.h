@@ -530,6 +530,44 @@ int dn_cheb_rows_per_workgroup(void);
 int dn_cheb_step_f64(const int32_t* rowptr, const int32_t* col, const double* val, int n_rows, const double* Y, const double* Z, double* out,
                      int nb, int ld, double alpha, double beta, double gamma, void* stream);
 
+/* ---- implicit diffusion (LearnedTimeDiffusion, method 'implicit_sparse'; reference layers.py:69-84 without the dense matrix): for every
+ *      mesh b and channel c the system (diag(m_b) + t_c L_b) x_bc = b_bc by Jacobi-preconditioned conjugate gradients (dn_implicit.hip).
+ *      rowptr [v_total + 1], col [nnz] int32, val [nnz] fp32: L in CSR over the concatenated vertex axis, block diagonal over the meshes,
+ *      columns in [0, v_total) (NOT checked here: the caller validates them); mass [v_total], time [C] (already clamped) fp32.
+ *      tiles [n_tiles][4] int32 (row0, nrows, mesh, 0) and mesh_tile_off [n_mesh + 1] int32, on the device: runs of at most
+ *      dn_implicit_rows_per_tile() rows of ONE mesh that cover [0, v_total) in order, and the first tile of every mesh (every mesh has at
+ *      least one row).  A tile is cut to the rows that exist: a wrong table gives wrong numbers, never an access outside the operands.
+ *      The blocks rhs, x0, out, x are fp32 row-major [v_total][C], contiguous.  All solver state (x, r, p, q, dot products, scalars) is
+ *      fp64 in the workspace, which the four calls of one solve share: dn_implicit_workspace_bytes(v_total, C, n_tiles, n_mesh) bytes.
+ *        init     b = m (.) rhs (rhs_mass != 0) or rhs; x = x0, or with x0 NULL b / m; r = b - A x, p = r / d, d = m + t diag(L) (the
+ *                 diagonal found by scanning each row; an empty row gives d = m); a system with ||r|| <= rtol ||b|| is done at once.
+ *        iterate  n_iter iterations, four launches each: q = A p and p.q | alpha, x += alpha p, r -= alpha q, r.z and r.r | beta, the
+ *                 iteration count, done | p = r / d + beta p.  Norms and dot products are per (mesh, channel), over that mesh's rows, summed
+ *                 in one fixed order without atomics: results repeat bit for bit.  A done system is frozen: further iterations change no
+ *                 bit of it.  A NaN or inf stays in its (mesh, channel).  unfinished: one device int32 that receives the number of systems
+ *                 not done after the call (n_iter == 0: only this); the caller reads it at its next synchronisation point.
+ *        finish   out = fp32(x), or fp32(m (.) x) with out_mass != 0; iterations [n_mesh][C] int32 and residual [n_mesh][C] fp64, the
+ *                 final ||r|| / ||b|| of the recurrence (either may be NULL).
+ *        lx_dot   d_time[c] = - sum over meshes, in mesh order, of g_bc . (L_b x_bc) with g the fp64 solution the workspace holds (the
+ *                 backward's solve) and x an fp32 block: the gradient of the diffusion times.
+ *      No allocation, no synchronisation, no memset nodes, no environment.  Every call returns 0 on success (v_total == 0 or C == 0:
+ *      nothing is launched, except that lx_dot with v_total == 0 stores zeros) and non-zero WITHOUT launching for a negative size, a NULL
+ *      required pointer, a workspace smaller than the query says, C > 65535 * 64, a tile table that cannot cover v_total (n_tiles *
+ *      dn_implicit_rows_per_tile() < v_total, n_tiles > v_total, or n_mesh > n_tiles), a negative or NaN rtol. */
+int dn_implicit_rows_per_tile(void);
+size_t dn_implicit_workspace_bytes(int v_total, int C, int n_tiles, int n_mesh);
+int dn_implicit_init_f32(const int32_t* rowptr, const int32_t* col, const float* val, const float* mass, const float* time, const int32_t* tiles,
+                         int n_tiles, const int32_t* mesh_tile_off, int n_mesh, int v_total, int C, const float* rhs, int rhs_mass, const float* x0,
+                         double rtol, void* ws, size_t ws_bytes, void* stream);
+int dn_implicit_iterate_f32(const int32_t* rowptr, const int32_t* col, const float* val, const float* mass, const float* time, const int32_t* tiles,
+                            int n_tiles, const int32_t* mesh_tile_off, int n_mesh, int v_total, int C, int n_iter, int32_t* unfinished, void* ws,
+                            size_t ws_bytes, void* stream);
+int dn_implicit_finish_f32(const float* mass, const int32_t* tiles, int n_tiles, const int32_t* mesh_tile_off, int n_mesh, int v_total, int C,
+                           int out_mass, float* out, int32_t* iterations, double* residual, void* ws, size_t ws_bytes, void* stream);
+int dn_implicit_lx_dot_f32(const int32_t* rowptr, const int32_t* col, const float* val, const int32_t* tiles, int n_tiles,
+                           const int32_t* mesh_tile_off, int n_mesh, int v_total, int C, const float* x, float* d_time, void* ws, size_t ws_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
