@@ -116,6 +116,11 @@ _SIGNATURES = {
     "dn_knn_max_k": (C.c_int, []),
     "dn_knn_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "dn_knn_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "dn_knn_grid_cells": (C.c_int, [C.c_int] * 4),
+    "dn_knn_grid_cell_budget": (C.c_int, []),
+    "dn_knn_grid_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "dn_knn_grid_keys_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "dn_knn_grid_search_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [C.c_int] * 5 + [_vp] * 7 + [_vp, C.c_size_t, _vp]),
     "dn_fps_resident_max_points": (C.c_int, []),
     "dn_fps_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dn_fps_f32": (C.c_int, [_vp, _vp] + [C.c_int] * 4 + [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -121,13 +121,19 @@ def find_knn(points_source, points_target, k, largest=False, omit_diagonal=False
     switch.  Other device tensors take a row-chunked torch path (the reference's difference formula; differentiable, as its ``'brute'`` branch); host tensors do what
     the reference does (``'brute'``: torch, ``'cpu_kd'``: ``sklearn.neighbors.KDTree``).
     Difference from the reference: with duplicate points and ``omit_diagonal`` its KD-tree branch may drop a duplicate other than the point
-    itself; the device routes always exclude index i.  The distances are identical."""
+    itself; the device routes always exclude index i.  The distances are identical.
+
+    ``method='grid'`` (not in the reference): where the cell-grid kernel applies -- the conditions above and D <= 3, no ``largest`` -- the
+    search is ``ops.knn_grid``, whose work grows with N k and whose result is ``ops.knn``'s bit for bit; everything else takes the route
+    ``'brute'`` takes."""
     if omit_diagonal and points_source.shape[0] != points_target.shape[0]:
         raise ValueError("omit_diagonal can only be used when source and target are same shape")
-    if method not in ("brute", "cpu_kd"):
+    if method not in ("brute", "cpu_kd", "grid"):
         raise ValueError("unrecognized method")
     if method == "cpu_kd" and largest:
         raise ValueError("can't do largest with cpu_kd")
+    if method == "grid" and largest:
+        raise ValueError("can't do largest with grid")
     if points_source.device != points_target.device:
         raise RuntimeError("find_knn: source points on %s, target points on %s" % (points_source.device, points_target.device))
     k = int(k)
@@ -136,9 +142,14 @@ def find_knn(points_source, points_target, k, largest=False, omit_diagonal=False
                and not points_source.requires_grad and not points_target.requires_grad)
         if not hip:
             return _knn_torch(points_source, points_target, k, largest, omit_diagonal)
+        grid = method == "grid" and points_source.dim() == 2 and points_source.shape[1] <= 3
         if torch.compiler.is_compiling():
-            from . import torchlib  # noqa: F401  (registers torch.ops.diffusion_net.knn)
+            from . import torchlib  # noqa: F401  (registers torch.ops.diffusion_net.knn, knn_grid)
+            if grid:
+                return KnnResult(*torch.ops.diffusion_net.knn_grid(points_source, points_target, k, bool(omit_diagonal), 0))
             return KnnResult(*torch.ops.diffusion_net.knn(points_source, points_target, k, bool(largest), bool(omit_diagonal)))
+        if grid:
+            return KnnResult(*ops.knn_grid(points_source, points_target, k, omit_diagonal))
         return KnnResult(*ops.knn(points_source, points_target, k, largest, omit_diagonal))
     if method == "cpu_kd":
         return _knn_kdtree(points_source, points_target, k, omit_diagonal)
@@ -278,6 +289,21 @@ def _cloud_on_device(verts, n_neighbors_cloud):
             and 1 <= int(n_neighbors_cloud) <= ops._hip.KNN_MAX_K)
 
 
+# Self-queries of clouds of at least this many points take the cell-grid search (``ops.knn_grid``: the same bits as ``ops.knn``, so the rule
+# changes speed only).  None: the rule is off, every self-query is ``ops.knn``.  Measured (tools/knn_grid_timing.py,
+# profiles/knn_grid_timing.txt): the smallest size from which the grid route is faster than brute force by more than twice the same-code
+# spread on both inputs, at that and every larger measured size -- 1.8 x at 10 000 points, 28 x and 30 x at 200 000; at 2 000 points the
+# uniform cube is slower on the grid (1.07 ms against 0.67 ms).
+KNN_GRID_MIN_POINTS = 10000
+
+
+def _cloud_self_knn(verts, k):
+    """[V, k] int64 neighbour table of a cloud among its own points for the device kernels (``_cloud_on_device(verts, k)`` holds)."""
+    if KNN_GRID_MIN_POINTS is not None and verts.shape[0] >= KNN_GRID_MIN_POINTS and verts.dim() == 2 and verts.shape[1] <= 3:
+        return ops.knn_grid(verts, verts, int(k), omit_diagonal=True)[1]
+    return ops.knn(verts, verts, int(k), omit_diagonal=True)[1]
+
+
 def _cloud_neighbors(verts, n_neighbors_cloud):
     """[V, k] numpy indices of the reference's neighbourhood query (geometry.py:119, :184)."""
     return find_knn(verts, verts, int(n_neighbors_cloud), omit_diagonal=True, method="cpu_kd").indices.detach().cpu().numpy()
@@ -299,7 +325,7 @@ def vertex_normals(verts, faces, n_neighbors_cloud=30):
         n = _pre.vertex_normals(verts.detach().cpu().numpy().astype("float64"), faces.detach().cpu().numpy().astype("int64"))
         normals = torch.from_numpy(n).to(device=verts.device, dtype=verts.dtype)
     elif _cloud_on_device(verts, n_neighbors_cloud):
-        nbr = ops.knn(verts, verts, int(n_neighbors_cloud), omit_diagonal=True)[1]
+        nbr = _cloud_self_knn(verts, n_neighbors_cloud)
         normals = ops.cloud_operators(verts, nbr)[0]
     else:
         normals = _cloud_normals_host(verts, n_neighbors_cloud)
@@ -337,7 +363,10 @@ def build_grad_point_cloud(verts, frames, n_neighbors_cloud=30):
     least-squares stencil over the edges to the ``n_neighbors_cloud`` nearest neighbours of i, real part X, imaginary part Y.  The
     result lives on the host, so only the neighbour query runs on the device (``find_knn``); the tangent coordinates are formed in the
     dtype of ``verts`` and the 2 x 2 systems solved in fp64, both as in the reference."""
-    nbr = find_knn(verts, verts, int(n_neighbors_cloud), omit_diagonal=True, method="cpu_kd").indices
+    if verts.is_cuda and _cloud_on_device(verts, n_neighbors_cloud) and not verts.requires_grad:   # (where find_knn runs ops.knn)
+        nbr = _cloud_self_knn(verts, n_neighbors_cloud)
+    else:
+        nbr = find_knn(verts, verts, int(n_neighbors_cloud), omit_diagonal=True, method="cpu_kd").indices
     return _grad_of_table(verts, frames, nbr)
 
 
@@ -372,7 +401,7 @@ def _cloud_operators_and_table(verts, n_neighbors_cloud, normals):
     V = verts.shape[0]
     if _cloud_on_device(verts, n_neighbors_cloud):
         k = int(n_neighbors_cloud)
-        nbr = ops.knn(verts, verts, k, omit_diagonal=True)[1]
+        nbr = _cloud_self_knn(verts, k)
         if normals is not None:
             normals = normals.to(device=verts.device, dtype=torch.float32)
         _, frames, _, col, vx, vy = ops.cloud_operators(verts, nbr, normals)
@@ -415,7 +444,7 @@ def point_cloud_laplacian(verts, n_neighbors=30, frames=None):
     and ``ops.cloud_laplacian`` (dn_knn.hip, dn_cloud.hip, dn_cloud_lap.hip) and never touch the host; everything else takes
     ``precompute.point_cloud_laplacian_host`` (vectorised numpy in fp64)."""
     if _cloud_on_device(verts, n_neighbors):
-        nbr = ops.knn(verts, verts, int(n_neighbors), omit_diagonal=True)[1]
+        nbr = _cloud_self_knn(verts, n_neighbors)
         if frames is None:
             frames = ops.cloud_operators(verts, nbr)[1]
         return _laplacian_of_table(verts, nbr, frames)

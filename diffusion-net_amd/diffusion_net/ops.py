@@ -258,6 +258,74 @@ def knn(src, tgt, k, largest=False, omit_diagonal=False, n_split=0):
 
 
 @_on_device
+def _knn_grid_launch(src, tgt, k, omit_diagonal, cells_per_axis, cell_budget, want_info):
+    """Every device step of ``knn_grid`` without a host read: bounds (torch), cell keys, stable sort of the keys and cell start table
+    (torch, as ``cloud_laplacian`` sorts its keys), gather + search."""
+    L = _hip.lib()
+    N, D = src.shape
+    M = tgt.shape[0]
+    dev = src.device
+    st = _hip.stream_of(src)
+    dist = torch.empty(N, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(N, k, dtype=torch.int64, device=dev)
+    info = torch.zeros(2, dtype=torch.int32, device=dev) if want_info else None
+    if N == 0:
+        return dist, idx, info
+    G = L.dn_knn_grid_cells(M, k, D, cells_per_axis)
+    shared = src.data_ptr() == tgt.data_ptr() and N == M         # a self-query: the sources' cells are the targets'
+    box = torch.cat((tgt.amin(dim=0), tgt.amax(dim=0)))
+    tkey = torch.empty(M, dtype=torch.int32, device=dev)
+    skey = None if shared else torch.empty(N, dtype=torch.int32, device=dev)
+    _hip.check(L.dn_knn_grid_keys_f32(src.data_ptr(), N, tgt.data_ptr(), M, D, k, cells_per_axis, box.data_ptr(), _hip.ptr(skey),
+                                      tkey.data_ptr(), st), "dn_knn_grid_keys_f32")
+    tsorted, torder = torch.sort(tkey, stable=True)
+    sorder = torder if shared else torch.sort(skey, stable=True)[1]
+    cells = torch.arange(G ** D + 1, dtype=torch.int32, device=dev)
+    cell_start = torch.searchsorted(tsorted, cells, out_int32=True)
+    ws = _hip.workspace(dev, L.dn_knn_grid_workspace_bytes(N, M, D, k, cells_per_axis))
+    _hip.check(L.dn_knn_grid_search_f32(src.data_ptr(), N, tgt.data_ptr(), M, D, k, int(omit_diagonal), cells_per_axis, cell_budget,
+                                        box.data_ptr(), sorder.data_ptr(), torder.data_ptr(), cell_start.data_ptr(), dist.data_ptr(),
+                                        idx.data_ptr(), _hip.ptr(info), ws.data_ptr(), ws.numel(), st), "dn_knn_grid_search_f32")
+    return dist, idx, info
+
+
+def knn_grid(src, tgt, k, omit_diagonal=False, cells_per_axis=0, return_info=False, cell_budget=None):
+    """``knn`` for D <= 3 by a search over a dense grid of cells (include/diffnet_hip.h: dn_knn_grid_search_f32): the same bits as
+    ``ops.knn(src, tgt, k, omit_diagonal=omit_diagonal)`` with work that grows with N k, forward only, no ``largest``.
+    ``cells_per_axis``: cells per axis of the grid (0: the library chooses from M, k and D); ``cell_budget``: cells a query may visit before
+    it scans all targets instead (None: the library's value; 0: every query scans) -- the result depends on neither.
+    ``return_info``: also return ``{'max_shell', 'full_scans', 'cells_per_axis'}`` of the call (reading it waits for the kernels; nothing
+    else in the call reads the host)."""
+    _hip.require_device(src)
+    _hip.require_device(tgt)
+    src, tgt = _f32c(src), _f32c(tgt)
+    if src.dim() != 2 or tgt.dim() != 2 or src.shape[1] != tgt.shape[1] or src.shape[1] < 1:
+        raise ValueError("knn takes [N, D] and [M, D] points (got %s and %s)" % (tuple(src.shape), tuple(tgt.shape)))
+    if src.shape[1] > 3:
+        raise ValueError("knn_grid takes points of at most 3 dimensions (got %d)" % src.shape[1])
+    if src.device != tgt.device:
+        raise RuntimeError("knn: source points on %s, target points on %s" % (src.device, tgt.device))
+    k, cells_per_axis = int(k), int(cells_per_axis)
+    if omit_diagonal and src.shape[0] != tgt.shape[0]:
+        raise ValueError("omit_diagonal can only be used when source and target are same shape")
+    if not 1 <= k <= _hip.KNN_MAX_K:
+        raise ValueError("knn kernel takes 1 <= k <= %d (got %d)" % (_hip.KNN_MAX_K, k))
+    if k > tgt.shape[0] - int(bool(omit_diagonal)):
+        raise ValueError("k = %d neighbours asked of %d candidates" % (k, tgt.shape[0] - int(bool(omit_diagonal))))
+    if cells_per_axis < 0:
+        raise ValueError("cells_per_axis must be >= 0")
+    budget = -1 if cell_budget is None else int(cell_budget)
+    if budget < -1:
+        raise ValueError("cell_budget must be >= 0")
+    dist, idx, info = _knn_grid_launch(src, tgt, k, bool(omit_diagonal), cells_per_axis, budget, bool(return_info))
+    if not return_info:
+        return dist, idx
+    shell, scans = info.tolist()
+    G = _hip.lib().dn_knn_grid_cells(tgt.shape[0], k, src.shape[1], cells_per_axis)
+    return dist, idx, {"max_shell": shell, "full_scans": scans, "cells_per_axis": G}
+
+
+@_on_device
 def _fps_launch(points, offsets, n_clouds, min_points, max_points, n_sample, start, route, return_min_dist):
     L = _hip.lib()
     dev = points.device

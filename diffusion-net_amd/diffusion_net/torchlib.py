@@ -299,6 +299,16 @@ def _(src, tgt, k, largest, omit_diagonal):
     return src.new_empty(src.shape[0], k, dtype=torch.float32), src.new_empty(src.shape[0], k, dtype=torch.int64)   # ops.knn is fp32
 
 
+@_op("diffusion_net::knn_grid")
+def knn_grid(src: Tensor, tgt: Tensor, k: int, omit_diagonal: bool, cells_per_axis: int) -> Tuple[Tensor, Tensor]:
+    return ops.knn_grid(src, tgt, k, omit_diagonal, cells_per_axis)
+
+
+@knn_grid.register_fake
+def _(src, tgt, k, omit_diagonal, cells_per_axis):
+    return src.new_empty(src.shape[0], k, dtype=torch.float32), src.new_empty(src.shape[0], k, dtype=torch.int64)
+
+
 # ------------------------------------------------------------------------------------------------ farthest point sampling (forward only)
 @_op("diffusion_net::fps")
 def fps(points: Tensor, n_sample: int) -> Tuple[Tensor, Tensor]:

@@ -339,6 +339,35 @@ size_t dn_knn_workspace_bytes(int n_src, int n_tgt, int dim, int k, int n_split)
 int dn_knn_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int largest, int omit_diagonal, int n_split,
                float* dist, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same search for dim <= 3 over a dense grid of cells (dn_knn_grid.hip): work grows with n_src k instead of n_src n_tgt, and
+ *      dist / idx are the bits dn_knn_f32 writes (same pair arithmetic, same order (squared distance, lower target index)) for every
+ *      cells_per_axis and every cell_budget, from run to run.  There is no `largest`.
+ *      The targets are binned into G = dn_knn_grid_cells(n_tgt, k, dim, cells_per_axis) cells per axis over their bounding cube
+ *      (cells_per_axis: 0 = the library's choice from (n_tgt, k, dim), > 0 = that many, clamped to 256 / 4096 / 2^22 for dim 3 / 2 / 1).
+ *      A call is two steps with the caller's sort between them; every operand stays on the device and nothing synchronises:
+ *        box [2 dim] fp32: the per-axis minimum, then the per-axis maximum, of tgt (computed by the caller);
+ *        dn_knn_grid_keys_f32 writes tgt_key [n_tgt] int32, the cell of every target, and src_key [n_src] (NULL: not wanted);
+ *        the caller provides tgt_order / src_order [n_tgt] / [n_src] int64, the permutations of a STABLE ascending sort of the keys, and
+ *        cell_start [G^dim + 1] int32, cell_start[c] = the number of targets whose key is below c;
+ *        dn_knn_grid_search_f32 gathers the targets in that order into the workspace and searches: every query visits the cells around
+ *        its own in shells of growing Chebyshev radius and stops when no unseen cell can hold a closer target.
+ *      cell_budget: a query that has visited more than this many cells without stopping scans all targets instead (< 0: the library's
+ *      value dn_knn_grid_cell_budget(); 0: every query scans).  info: NULL, or two int32 words the caller zeroed -- the largest shell
+ *      radius any query reached and the number of queries that scanned.
+ *      Non-finite coordinates give unspecified neighbours but no out-of-range access and no unbounded loop (an index read from
+ *      tgt_order / src_order / cell_start is clamped into range).
+ *      Both calls return 0 on success (n_src == 0: the search launches nothing) and non-zero WITHOUT launching for dim outside 1..3,
+ *      k < 1, k > DN_KNN_MAX_K, a negative size or cells_per_axis, a NULL required pointer; the search also for
+ *      k > n_tgt - (omit_diagonal ? 1 : 0), omit_diagonal with n_src != n_tgt, or a workspace smaller than the query says. */
+int dn_knn_grid_cells(int n_tgt, int k, int dim, int cells_per_axis);
+int dn_knn_grid_cell_budget(void);
+size_t dn_knn_grid_workspace_bytes(int n_src, int n_tgt, int dim, int k, int cells_per_axis);
+int dn_knn_grid_keys_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int cells_per_axis, const float* box,
+                         int32_t* src_key, int32_t* tgt_key, void* stream);
+int dn_knn_grid_search_f32(const float* src, int n_src, const float* tgt, int n_tgt, int dim, int k, int omit_diagonal, int cells_per_axis,
+                           int cell_budget, const float* box, const int64_t* src_order, const int64_t* tgt_order, const int32_t* cell_start,
+                           float* dist, int64_t* idx, int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- geometry.farthest_point_sampling (geometry.py:727-751): farthest point sampling with the sample loop on the device (dn_fps.hip).
  *      pts [V, 3] fp32 row-major, already normalised: one cloud, or n_clouds clouds packed back to back with offsets [n_clouds + 1] int64
  *      ON THE DEVICE (cloud c is rows offsets[c] .. offsets[c+1] - 1).  order [n_clouds, n_sample] int64: rows of the packed array in the

@@ -9,6 +9,8 @@
 #   c256         BASELINE config 4's width: kbench block tables chained / unfused at C = 256, the C = 256 parity cases, bench.py --config cfg4
 #   kbench       block_inf / block_fwd / block_bwd / diffusion tables (tools/kbench --check)
 #   knn          ops.knn at the two find_knn workload shapes against chunked cdist + topk and the host KD-tree (tools/knn_timing.py)
+#   knn_grid     ops.knn_grid against ops.knn in alternating windows on sphere vertices and a uniform cube, 2 000 to 1 000 000 points, the
+#                grid route's steps, its counters, point_cloud_laplacian on both routes -> knn_grid_timing.txt (tools/knn_grid_timing.py)
 #   fps          farthest point sampling at four shapes: the resident route, the stepped route and the torch route on the same device,
 #                time per sample and launches per call -> fps_timing.txt (tools/fps_timing.py)
 #   cloud        ops.knn and the point-cloud pass dn_cloud_operators_f32 at 10 000 and 200 000 points, host route at 10 000; the local-Delaunay
@@ -76,6 +78,8 @@ kbench)
   $KB --check "$@" 2>&1 | cut -c1-200 | tee $OUT/kbench.txt ;;
 knn)
   timeout 300 python tools/knn_timing.py ;;
+knn_grid)
+  timeout 900 python tools/knn_grid_timing.py ;;
 fps)
   timeout 300 python tools/fps_timing.py ;;
 cloud)
